@@ -19,9 +19,15 @@ are timed with HIP events on the stream they run on (cfws.TimingEvent:
 created without the system-scope fence, which torch.cuda.Event records and
 which left ~6 us of idle GPU in the stream at each record).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
          (N > 1: this process starts N workers itself, one per GPU, and makes
           no GPU call; spawn_ranks)
+A plain run sets up, warms up, times the K steps and prints the line; the
+kernel and roofline figures in it come from events recorded inside those
+steps. --full adds what takes runs of its own: the check of what was timed
+(`verified`, which also sets the exit status), the copy ceiling and the CPU
+baseline. --dump-outputs DIR writes what the last timed step produced as
+DIR/<name>.npy (dump_outputs).
        torchrun --nproc-per-node N bench.py --gpus N ...   (the same run under torchrun)
 The ranks' bookkeeping collectives run over gloo (RCCL is never initialised).
 """
@@ -53,9 +59,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--frames", type=int, default=65536, help="frames per GPU")
     ap.add_argument("--frame-size", type=int, default=65536)
+    ap.add_argument("--full", action="store_true",
+                    help="also check what was timed (verified; a failed check exits 1) and "
+                         "measure the copy ceiling and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy "
+                         "(float32 / float64, a seeded sample of the large ones)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="target CPU time of the cpu_baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: target CPU time of the cpu_baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: only the multi-rank launch and bookkeeping (CPU test)")
     ap.add_argument("--recv-slots", action="store_true",
@@ -248,6 +260,37 @@ def cpu_baseline_h2(frame_size: int, max_frame: int, seconds: float):
     }
 
 
+DUMP_BUDGET = 60 << 20         # bytes of array data one --dump-outputs run may write
+DUMP_BLOCK = 4096              # a sampled output is read in runs of this many elements
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_outputs(path: str, outputs: dict, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: the tensors the timed path handed its caller in the
+    last timed step, one DIR/<name>.npy each (<name>.rank<r>.npy with more
+    than one rank). Bytes and 16-bit integers are stored as float32, wider
+    integers as float64 (exact below 2^53). Every array gets an equal share
+    of DUMP_BUDGET; one that is larger is sampled in DUMP_BLOCK-element runs
+    at seeded places, the same places in every run with the same arguments,
+    in ascending order."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // max(world, 1) // max(len(outputs), 1)
+    for i, (name, t) in enumerate(outputs.items()):
+        t = t.reshape(-1)
+        wide = t.element_size() > 2
+        cap = share // (8 if wide else 4)
+        if t.numel() > cap:
+            blocks = max(1, cap // DUMP_BLOCK)
+            rng = np.random.default_rng([DUMP_SEED, i])
+            first = np.sort(rng.choice(t.numel() // DUMP_BLOCK, blocks, replace=False)) * DUMP_BLOCK
+            at = torch.from_numpy(first).to(t.device)[:, None] + torch.arange(DUMP_BLOCK, device=t.device)
+            t = t[at.reshape(-1)]
+        a = t.cpu().numpy().astype(np.float64 if wide else np.float32)
+        np.save(os.path.join(path, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def size_label(n: int) -> str:
     """64 KiB, 1 KiB, 256 B, 16376 B: the frame size as the workload names it."""
     return f"{n // 1024} KiB" if n >= 1024 and n % 1024 == 0 else f"{n} B"
@@ -347,9 +390,15 @@ def bench_h2(args, rank, world, dev):
     dom_ms = max(send_ms, recv_ms)
     achieved = alg / (dom_ms * 1e-3) / 1e9
     rows = shard.gather_floats([local, F * fs], dev)
-    ok = (m == F and int(ptot.item()) == F * fs and bool((st == 0).all()) and bool((ms == 0).all())
-          and torch.equal(back[:F * fs], payload[:F * fs]))
-    ok = shard.sum_over_ranks(1.0 if ok else 0.0, dev) == world
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"h2": h2[:h2_total], "h2_total": tot, "data_frame_status": st,
+                                         "message_desc": md, "message_status": ms, "payload_total": ptot,
+                                         "payload": back[:F * fs]}, rank, world)
+    ok = None
+    if args.full:
+        ok = (m == F and int(ptot.item()) == F * fs and bool((st == 0).all()) and bool((ms == 0).all())
+              and torch.equal(back[:F * fs], payload[:F * fs]))
+        ok = shard.sum_over_ranks(1.0 if ok else 0.0, dev) == world
     line = {"metric": "WS-over-HTTP/2 payload GiB/s device-resident (config 5)",
             "value": round(2.0 * F * fs * world * args.steps / elapsed / GIB, 2), "unit": "GiB/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -366,13 +415,13 @@ def bench_h2(args, rank, world, dev):
             "kernels": kern,
             "note": "one fused streaming pass per direction: WS frames straight into DATA frames (send), WS payload slices straight out of DATA frames (receive)",
             "per_gpu": per_gpu_rows(rows, args.steps), "verified": ok}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_h2(fs, S, args.cpu_seconds)
     else:
         line["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(line), flush=True)
-    return 0 if ok else 1
+    return 1 if ok is False else 0
 
 
 def bench_split(args, rank, world, dev):
@@ -424,7 +473,10 @@ def bench_split(args, rank, world, dev):
     local = time.perf_counter() - t0
     elapsed = shard.max_over_ranks(local, dev)
     rows = shard.gather_floats([local, F * fs], dev)
-    ok = bool((st_t == 0).all()) and torch.equal(back, payload)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"wire": wire[:wire_total], "frame_desc": pd_t, "frame_status": st_t,
+                                         "payload": back}, rank, world)
+    ok = bool((st_t == 0).all()) and torch.equal(back, payload) if args.full else None
     line = {"metric": "WS payload mask/unmask GiB/s device-resident, split ops (config 2 layout)",
             "value": round(2.0 * F * fs * world * args.steps / elapsed / GIB, 2), "unit": "GiB/s",
             "n_gpus": world, "steps": args.steps, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -433,7 +485,7 @@ def bench_split(args, rank, world, dev):
             "per_gpu": per_gpu_rows(rows, args.steps), "verified": ok}
     if rank == 0:
         print(json.dumps(line), flush=True)
-    return 0 if ok else 1
+    return 1 if ok is False else 0
 
 
 VALU_PEAK_OPS = 256 * 4 * 32 * 2.4e9     # lane-ops/s: 256 CUs x 4 SIMDs x 32 lanes/clk x 2.4 GHz
@@ -496,11 +548,15 @@ def bench_accept(args, rank, world, dev):
     elapsed = shard.max_over_ranks(local, dev)
     kms = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
     del ev                                   # HIP events freed while the runtime is up
-    h = out.view(N, cfws.WS_ACCEPT_SLOT)
-    sample = list(range(0, N, max(1, N // 4096)))
-    got = h[sample, :28].cpu().numpy()
-    ok = all(bytes(got[j]).decode() == O.ws_accept_key(keys[i]) for j, i in enumerate(sample))
-    ok = shard.sum_over_ranks(1.0 if ok else 0.0, dev) == world
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accept_keys": out}, rank, world)
+    ok = None
+    if args.full:
+        h = out.view(N, cfws.WS_ACCEPT_SLOT)
+        sample = list(range(0, N, max(1, N // 4096)))
+        got = h[sample, :28].cpu().numpy()
+        ok = all(bytes(got[j]).decode() == O.ws_accept_key(keys[i]) for j, i in enumerate(sample))
+        ok = shard.sum_over_ranks(1.0 if ok else 0.0, dev) == world
     # VALU lane-ops per key from the committed PMC pass (SQ_INSTS_VALU x 64 /
     # keys, measured at 1,048,576 keys; per key, so it scales with --keys)
     per_key = load_pmc("pmc_accept.json", "valu_instructions_per_key")
@@ -517,7 +573,7 @@ def bench_accept(args, rank, world, dev):
                          "frac": round(achieved / VALU_PEAK_OPS, 4) if achieved else None,
                          "valu_lane_ops_per_launch": per_key * N if per_key else None},
             "verified": ok}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         kind = "reference" if O.ref_lib("O2") is not None else "port"
         threads = effective_cpus()
         n = min(N, 262144)
@@ -531,7 +587,7 @@ def bench_accept(args, rank, world, dev):
                                 "seconds": round(t, 2)}
     if rank == 0:
         print(json.dumps(line), flush=True)
-    return 0 if ok else 1
+    return 1 if ok is False else 0
 
 
 def bench_index(args, rank, world, dev):
@@ -600,15 +656,20 @@ def bench_index(args, rank, world, dev):
     kms = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
     del ev                                   # HIP events freed while the runtime is up
     n_frames = int(total.item())
-    host_wire = wire[:wtotal].cpu().numpy()
-    st_h, first_h = starts_t.cpu().numpy(), first.cpu().numpy()
-    con_h, stop_h = consumed.cpu().numpy(), stop.cpu().numpy()
-    ok = True
-    for c in range(0, C_, max(1, C_ // 256)):
-        e_st, e_con, e_stop = O.index_stream(host_wire, int(begin_np[c]), int(end_np[c]))
-        ok &= bool(np.array_equal(st_h[first_h[c]:first_h[c] + len(e_st)].astype(np.uint64), e_st)
-                   and con_h[c] == e_con and stop_h[c] == e_stop)
-    ok = shard.sum_over_ranks(1.0 if ok else 0.0, dev) == world
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"starts": starts_t[:n_frames], "first": first, "consumed": consumed,
+                                         "stop": stop, "total": total}, rank, world)
+    ok = None
+    if args.full:
+        host_wire = wire[:wtotal].cpu().numpy()
+        st_h, first_h = starts_t.cpu().numpy(), first.cpu().numpy()
+        con_h, stop_h = consumed.cpu().numpy(), stop.cpu().numpy()
+        ok = True
+        for c in range(0, C_, max(1, C_ // 256)):
+            e_st, e_con, e_stop = O.index_stream(host_wire, int(begin_np[c]), int(end_np[c]))
+            ok &= bool(np.array_equal(st_h[first_h[c]:first_h[c] + len(e_st)].astype(np.uint64), e_st)
+                       and con_h[c] == e_con and stop_h[c] == e_stop)
+        ok = shard.sum_over_ranks(1.0 if ok else 0.0, dev) == world
     hops = n_frames / C_
     line = {"metric": "WS receive-buffer frame indexing frames/s, many connections, device resident",
             "value": round(n_frames * world * args.steps / elapsed, 1), "unit": "frames/s",
@@ -628,7 +689,7 @@ def bench_index(args, rank, world, dev):
                                  "length, not HBM bytes",
                          "ns_per_hop": round(kms * 1e6 / max(hops, 1e-9), 1)},
             "verified": ok}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         threads = effective_cpus()
         ub = (begin_np.astype(np.uint64), end_np.astype(np.uint64))
         t1, _ = O.cpu_index_bench(host_wire, ub[0], ub[1], 4096, threads)
@@ -645,7 +706,7 @@ def bench_index(args, rank, world, dev):
                                 "seconds": round(t, 2)}
     if rank == 0:
         print(json.dumps(line), flush=True)
-    return 0 if ok else 1
+    return 1 if ok is False else 0
 
 
 def per_gpu_rows(rows, steps: int):
@@ -937,50 +998,67 @@ def main():
     local = time.perf_counter() - t0
     elapsed = shard.max_over_ranks(local, dev)
 
-    # correctness of what was timed: unmask(mask(P)) == P, every frame COMPLETE
-    if info_t is not None:
-        # the compact entries: payload_size, fin 1, opcode BINARY, status COMPLETE
-        exp = fs | 1 << 32 | cfws.OPCODE_BINARY << 40
-        ok_info = bool((info_t.view(torch.int64).view(-1) == exp).all().item())
+    if args.dump_outputs:
+        # before the checks and the copy ceiling below, which write to these buffers
+        outs = {"wire": wire[:wire_total], "wire_total": tot_ser,
+                "payload": (back[:F * pstride].view(F, pstride)[:, :fs] if pstride != fs and not slot
+                            else back[:arena_bytes])}
+        if info_t is not None:
+            outs["frame_info"] = info_t
+        else:
+            outs["frame_desc"], outs["frame_status"] = desc_de, status
+        if perm is None:                # the scatter receive reports no total
+            outs["payload_total"] = tot_de
         if mismatch_t is not None:
-            ok_info = ok_info and int(mismatch_t.item()) == 0
-        status.fill_(0 if ok_info else 1)
-        if perm is None:
-            tot_de.fill_(arena_bytes)
-    if perm is not None:
-        # frame i's payload is slot perm[i]: gather the slots back into frame order
-        got = back[:arena_bytes].view(F, slot)[perm]
-        verified = (int(tot_ser.item()) == wire_total and bool((status == 0).all().item())
-                    and torch.equal(got.reshape(-1), payload[:arena_bytes]))
-        del got
-    elif pstride != fs and not slot:
-        verified = (int(tot_ser.item()) == wire_total and int(tot_de.item()) == F * pstride
-                    and bool((status == 0).all().item())
-                    and torch.equal(back[:F * pstride].view(F, pstride)[:, :fs], payload[:arena_bytes].view(F, fs)))
-    else:
-        verified = (int(tot_ser.item()) == wire_total and int(tot_de.item()) == arena_bytes
-                    and bool((status == 0).all().item())
-                    and torch.equal(back[:arena_bytes], payload[:arena_bytes]))
-    verified = shard.sum_over_ranks(1.0 if verified else 0.0, dev) == world
+            outs["mismatch"] = mismatch_t
+        dump_outputs(args.dump_outputs, outs, rank, world)
 
-    # practical ceiling: a bare streaming copy of the same byte count
-    # (cfws_device_copy: the best shape of tools/copy_probe.hip), and
-    # torch's copy_ beside it
-    def copy_rate(fn, reps=5):
-        fn()
-        c0, c1 = cfws.TimingEvent(), cfws.TimingEvent()
-        c0.record()
-        for _ in range(reps):
+    verified = None
+    if args.full:
+        # correctness of what was timed: unmask(mask(P)) == P, every frame COMPLETE
+        if info_t is not None:
+            # the compact entries: payload_size, fin 1, opcode BINARY, status COMPLETE
+            exp = fs | 1 << 32 | cfws.OPCODE_BINARY << 40
+            ok_info = bool((info_t.view(torch.int64).view(-1) == exp).all().item())
+            if mismatch_t is not None:
+                ok_info = ok_info and int(mismatch_t.item()) == 0
+            status.fill_(0 if ok_info else 1)
+            if perm is None:
+                tot_de.fill_(arena_bytes)
+        if perm is not None:
+            # frame i's payload is slot perm[i]: gather the slots back into frame order
+            got = back[:arena_bytes].view(F, slot)[perm]
+            verified = (int(tot_ser.item()) == wire_total and bool((status == 0).all().item())
+                        and torch.equal(got.reshape(-1), payload[:arena_bytes]))
+            del got
+        elif pstride != fs and not slot:
+            verified = (int(tot_ser.item()) == wire_total and int(tot_de.item()) == F * pstride
+                        and bool((status == 0).all().item())
+                        and torch.equal(back[:F * pstride].view(F, pstride)[:, :fs], payload[:arena_bytes].view(F, fs)))
+        else:
+            verified = (int(tot_ser.item()) == wire_total and int(tot_de.item()) == arena_bytes
+                        and bool((status == 0).all().item())
+                        and torch.equal(back[:arena_bytes], payload[:arena_bytes]))
+        verified = shard.sum_over_ranks(1.0 if verified else 0.0, dev) == world
+
+        # practical ceiling: a bare streaming copy of the same byte count
+        # (cfws_device_copy: the best shape of tools/copy_probe.hip), and
+        # torch's copy_ beside it
+        def copy_rate(fn, reps=5):
             fn()
-        c1.record()
-        torch.cuda.synchronize()
-        ms = c0.elapsed_time(c1) / reps
-        del c0, c1
-        return 2 * payload.numel() / (ms * 1e-3) / 1e9
+            c0, c1 = cfws.TimingEvent(), cfws.TimingEvent()
+            c0.record()
+            for _ in range(reps):
+                fn()
+            c1.record()
+            torch.cuda.synchronize()
+            ms = c0.elapsed_time(c1) / reps
+            del c0, c1
+            return 2 * payload.numel() / (ms * 1e-3) / 1e9
 
-    n_copy = payload.numel() // 16 * 16
-    copy_gbps = copy_rate(lambda: cfws.device_copy(payload, back, n_copy))
-    torch_copy_gbps = copy_rate(lambda: back[:payload.numel()].copy_(payload))
+        n_copy = payload.numel() // 16 * 16
+        copy_gbps = copy_rate(lambda: cfws.device_copy(payload, back, n_copy))
+        torch_copy_gbps = copy_rate(lambda: back[:payload.numel()].copy_(payload))
 
     ser_each = [e[0].elapsed_time(e[1]) for e in events]
     de_each = [e[2].elapsed_time(e[3]) for e in events]
@@ -1063,14 +1141,16 @@ def main():
         },
         "kernels": kern,
         "per_gpu": per_gpu_rows(rows, args.steps),
-        "copy_ceiling": {"GBps": round(copy_gbps, 1), "frac_of_copy": round(achieved / copy_gbps, 4),
-                         "how": "cfws_device_copy of the payload arena, device to device (nt loads "
-                                "and stores, 2 KiB per wave, 4 WG/CU: tools/copy_probe.hip's best "
-                                "shape)",
-                         "torch_copy_GBps": round(torch_copy_gbps, 1)},
-        "verified": verified,
+        "copy_ceiling": None,           # --full
+        "verified": verified,           # --full
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "config2":
+    if args.full:
+        line["copy_ceiling"] = {"GBps": round(copy_gbps, 1), "frac_of_copy": round(achieved / copy_gbps, 4),
+                                "how": "cfws_device_copy of the payload arena, device to device (nt loads "
+                                       "and stores, 2 KiB per wave, 4 WG/CU: tools/copy_probe.hip's best "
+                                       "shape)",
+                                "torch_copy_GBps": round(torch_copy_gbps, 1)}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "config2":
         line["cpu_baseline"] = cpu_baseline(fs, args.cpu_seconds)
     else:
         line["cpu_baseline"] = None
@@ -1078,7 +1158,7 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
-    if not verified:
+    if verified is False:
         sys.exit(1)
 
 

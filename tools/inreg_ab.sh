@@ -12,7 +12,7 @@ if [ -z "$NOTEST" ]; then
 fi
 run() {  # name knob args...
   local name=$1 k=$2; shift 2
-  CFWS_SER_INREG=$k timeout -k 10 200 python3 bench.py --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
+  CFWS_SER_INREG=$k timeout -k 10 200 python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
   local rc=$?
   [ $rc -ne 0 ] && { echo "$name rc=$rc"; tail -3 "$OUT/$name.err"; exit $rc; }
   python3 -c "import json,sys; d=json.loads(open('$OUT/$name.json').read().strip().splitlines()[-1]); print('$name', d['value'], d['kernels'])"

@@ -8,5 +8,5 @@ OUT=$R/gpurun_out/${TAG:-ks}; mkdir -p "$OUT"
 for v in base $VARIANTS; do
   L=$R/coldforce_amd/libcfws.so; [ $v = base ] || L=$R/build/variants/libcfws_$v.so
   CFWS_LIB=$L timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ks_$v" -o ks -- \
-    python3 $R/bench.py ${ARGS:---workload split} --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/ks_$v.log" 2>&1 || exit 1
+    python3 $R/bench.py ${ARGS:---workload split} --steps 10 --warmup 3 --full --no-cpu-baseline > "$OUT/ks_$v.log" 2>&1 || exit 1
 done

@@ -9,6 +9,6 @@ export TMPDIR=/tmp
 cd /tmp
 for w in ${WORKLOADS:-config2}; do
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$w" -o kt -- \
-      python3 $R/bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --workload $w > "$OUT/$w.log" 2>&1 || exit 1
+      python3 $R/bench.py --steps ${STEPS:-10} --warmup 2 --full --no-cpu-baseline --workload $w > "$OUT/$w.log" 2>&1 || exit 1
 done
 echo done

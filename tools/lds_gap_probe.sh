@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/${TAG:-ldsgap}; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() {
   local name=$1; shift
-  env "$@" timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/$name -o kt -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || exit 1
+  env "$@" timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/$name -o kt -- python3 $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || exit 1
 }
 case "${SET:-1}" in
 1)

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/${TAG:-pmcdir}
 mkdir -p "$OUT"
 run() {
   timeout -s KILL 120 rocprofv3 --pmc $2 --output-format csv -d "$OUT/$1" -o $1 -- \
-    python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/$1.log" 2>&1
+    python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > "$OUT/$1.log" 2>&1
 }
 run sq "SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_SMEM SQ_BUSY_CYCLES" &&
 run tcc "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum" &&

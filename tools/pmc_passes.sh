@@ -11,5 +11,5 @@ IFS=';' read -ra SETS <<< "$PASSES"
 for C in "${SETS[@]}"; do
   i=$((i+1))
   timeout -s KILL 120 rocprofv3 --pmc $C --output-format csv -d "$OUT/p$i" -o p -- \
-    python3 $R/bench.py ${ARGS:---workload split} --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/p$i.log" 2>&1 || exit 1
+    python3 $R/bench.py ${ARGS:---workload split} --steps 2 --warmup 1 --full --no-cpu-baseline > "$OUT/p$i.log" 2>&1 || exit 1
 done

@@ -18,7 +18,7 @@ for wl in config2 config3 config5 split index accept fs1k; do
   esac
   port=$((port + 1))
   timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-      --master-port $port bench.py --gpus $N --steps 5 --warmup 2 --no-cpu-baseline $a > "$OUT/${wl}_n$N.log" 2>&1
+      --master-port $port bench.py --gpus $N --steps 5 --warmup 2 --full --no-cpu-baseline $a > "$OUT/${wl}_n$N.log" 2>&1
   rc=$?
   echo "== $wl n=$N rc=$rc"
   grep '^{' "$OUT/${wl}_n$N.log" | tail -1 | cut -c1-220

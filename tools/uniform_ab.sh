@@ -19,7 +19,7 @@ for r in 1 2; do
       esac
       tag=${v%%=*}
       env CFWS_LIB=$L $E timeout -k 10 200 python3 bench.py --frames $F --frame-size $fs --send uniform \
-          ${RECV:---recv-slots --recv-info} --no-cpu-baseline --steps 10 --warmup 3 > "$OUT/fs${fs}_${tag}_r$r.json" 2> "$OUT/fs${fs}_${tag}_r$r.err" \
+          ${RECV:---recv-slots --recv-info} --full --no-cpu-baseline --steps 10 --warmup 3 > "$OUT/fs${fs}_${tag}_r$r.json" 2> "$OUT/fs${fs}_${tag}_r$r.err" \
           || { echo "fs$fs $v failed"; exit 1; }
       python3 -c "import json; d=json.loads(open('$OUT/fs${fs}_${tag}_r$r.json').read().strip().splitlines()[-1]); k=d['kernels']; print('fs${fs}', '$tag', 'r$r', d['verified'], k['serialize_execute']['ms'], k['deserialize_execute']['ms'])"
     done

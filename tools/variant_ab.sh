@@ -9,7 +9,7 @@ run() {
   for round in 1 2; do
     for v in base $VARIANT; do
       L=$PWD/coldforce_amd/libcfws.so; [ $v = base ] || L=$PWD/build/variants/libcfws_$v.so
-      CFWS_LIB=$L timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" \
+      CFWS_LIB=$L timeout -k 10 300 python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline "$@" \
         > "$OUT/${name}_${v}_r$round.json" 2> "$OUT/${name}_${v}_r$round.err" || { echo "$name $v failed"; exit 1; }
     done
   done

@@ -16,7 +16,7 @@ for r in 1 2; do
     L=$PWD/coldforce_amd/libcfws.so; [ $v = base ] || L=$PWD/build/variants/libcfws_$v.so
     for w in "fs1k --frames 4194304 --frame-size 1024" "fs256 --frames 16777216 --frame-size 256" "c2" "c3 --workload config3"; do
       set -- $w; name=$1; shift
-      CFWS_LIB=$L timeout -k 10 200 python3 bench.py --no-cpu-baseline "$@" > "$OUT/${name}_${v}_r$r.json" 2> "$OUT/${name}_${v}_r$r.err" || { echo "$name $v failed"; exit 1; }
+      CFWS_LIB=$L timeout -k 10 200 python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/${name}_${v}_r$r.json" 2> "$OUT/${name}_${v}_r$r.err" || { echo "$name $v failed"; exit 1; }
       python3 -c "import json; d=json.loads(open('$OUT/${name}_${v}_r$r.json').read().strip().splitlines()[-1]); k=d['kernels']; print('${name}_${v}_r$r', d['value'], k['serialize_execute']['ms'], k['deserialize_execute']['ms'])"
     done
   done
