@@ -2,7 +2,8 @@
 // (include/cfws.h: serialize / deserialize plan, execute, batch), its plan
 // kernels and the single-launch small-batch kernels, and the library's
 // error state. The streaming kernel and the device code the units share are
-// in cfws_kernels.h; HTTP/2 in cfws_h2.hip; the smaller ops in cfws_ops.hip.
+// in cfws_kernels.h; the receive into fixed slots in cfws_slots.hip; HTTP/2
+// in cfws_h2.hip; the smaller ops in cfws_ops.hip.
 //
 // Reference behaviour restated on the device:
 //   header encode        co_ws_frame.c:34-68, :70-91
@@ -31,7 +32,6 @@
 #include "cfws_kernels.h"
 
 #include <mutex>
-#include <type_traits>
 
 namespace cfws_rt {
 
@@ -479,18 +479,10 @@ serialize_plan_single_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t* __r
 // copy streams next (one pass over the wire instead of two: the plan alone
 // re-read 0.5 GB of 128-byte lines for 4 M x 1 KiB frames, 2.2 GB for
 // 16 M x 256 B). Wave w copies the frames it parsed (item k, lane l: frame
-// k * 64 + l of its run). Per item, the wave's largest slot sets how many
-// frames share one wave-instruction: groups of G lanes (G x 16 bytes >= the
-// slot), one frame per group; items with a slot over 1 KiB go frame by
-// frame, 1 KiB per instruction. A lane's chunk is its frame's source block
-// funnel-shifted with the next lane's block over DPP (the lane loads the
-// next block itself at its group's end), XORed with the key (each chunk
-// starts at a payload index that is a multiple of 16, so the key needs no
-// rotation) and masked past the payload: every slot byte below the pass
-// total is written once, payload or zero, as the plan + execute write it.
-#ifndef CFWS_FUSED_UNROLL
-#define CFWS_FUSED_UNROLL 4
-#endif
+// k * 64 + l of its run) with fused_item (cfws_kernels.h, shared with the
+// slot receive): every slot byte below the pass total is written once,
+// payload or zero, as the plan + execute write it.
+//
 // The fused kernel's occupancy hint, stated as what it is: workgroups of
 // kFusedThreads per CU (__launch_bounds__' second argument). 1 at 1024
 // threads = 16 waves per CU, 4 per SIMD: the register budget every fused
@@ -501,121 +493,6 @@ serialize_plan_single_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t* __r
 #endif
 constexpr int kFusedMinBlocksPerCU = CFWS_FUSED_MIN_BLOCKS_PER_CU;
 static_assert(kFusedMinBlocksPerCU >= 1, "the fused kernel's occupancy hint must be at least 1");
-constexpr int kFusedUnroll = CFWS_FUSED_UNROLL;   // rounds of loads in flight per wave
-
-__device__ __forceinline__ void fused_store(uint8_t* __restrict__ out, uint64_t D, uint64_t total, uint4 o)
-{
-    if (D + 16 <= total) {
-        st16(out + D, o);
-    } else {
-        for (uint32_t j = 0; D + j < total; ++j) {
-            const uint32_t w = j < 4 ? o.x : (j < 8 ? o.y : (j < 12 ? o.z : o.w));
-            out[D + j] = (uint8_t)(w >> (8 * (j & 3)));
-        }
-    }
-}
-
-// One lane's chunk in a round: its destination D and source s, the bytes
-// of the slot it writes (nbytes) and of those the payload (need), the key.
-struct FusedChunk {
-    uint64_t D, s;
-    uint32_t need, nbytes, key;
-};
-
-template <int kUnroll = kFusedUnroll>
-__device__ __forceinline__ void fused_item(const uint8_t* __restrict__ wire, uint8_t* __restrict__ out,
-                                           uint64_t total, uint64_t run, uint64_t src, uint32_t len,
-                                           uint32_t nb, uint32_t key, uint32_t lane)
-{
-    // wave-wide largest slot
-    uint32_t m = nb;
-#pragma unroll
-    for (uint32_t o = 32; o >= 1; o >>= 1) {
-        const uint32_t y = (uint32_t)__shfl_xor((int)m, o, 64);
-        m = y > m ? y : m;
-    }
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    if (m == 0) return;
-    if (m <= 1024) {
-        // G lanes per frame (G x 16 >= m), P = 64 / G frames per round
-        uint32_t G = 1;
-        while (G * 16 < m) G <<= 1;
-        const uint32_t P = 64 / G, g = lane / G, c = lane % G;
-        for (uint32_t r0 = 0; r0 < G; r0 += kUnroll) {
-            uint4 A[kUnroll], E[kUnroll];
-            FusedChunk q[kUnroll];
-            bool nl[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const uint32_t r = r0 + u;
-                const int fl = (int)((r < G ? r : 0) * P + g);
-                const uint64_t runj = __shfl(run, fl, 64), srcj = __shfl(src, fl, 64);
-                const uint32_t lenj = (uint32_t)__shfl((int)len, fl, 64);
-                const uint32_t nbj = r < G ? (uint32_t)__shfl((int)nb, fl, 64) : 0u;
-                q[u].key = (uint32_t)__shfl((int)key, fl, 64);
-                q[u].D = runj + 16 * c;
-                q[u].s = srcj + 16 * c;
-                q[u].nbytes = 16 * c < nbj ? (uint32_t)(nbj - 16 * c < 16 ? nbj - 16 * c : 16) : 0u;
-                q[u].need = q[u].nbytes && 16 * c < lenj ? (uint32_t)(lenj - 16 * c < 16 ? lenj - 16 * c : 16) : 0u;
-                nl[u] = c + 1 < G && 16 * (c + 1) < lenj;          // the next lane loads the next block
-                const uint32_t ph = (uint32_t)(q[u].s & 15u);
-                A[u] = q[u].need ? ld16(wire + (q[u].s & ~uint64_t(15))) : z;
-                E[u] = q[u].need && ph && !nl[u] && ph + q[u].need > 16
-                           ? ld16(wire + (q[u].s & ~uint64_t(15)) + 16) : z;
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const uint4 nb4 = from_next_lane(A[u], E[u]);      // every lane: DPP needs the full wave
-                if (!q[u].nbytes) continue;
-                const uint32_t ph = (uint32_t)(q[u].s & 15u);
-                uint4 o = z;
-                if (q[u].need) {
-                    o = ph ? funnel16(A[u], nl[u] ? nb4 : E[u], ph) : A[u];
-                    xor4(o, q[u].key);
-                    if (q[u].need < 16) o = and4(o, byte_range(0, q[u].need));
-                }
-                fused_store(out, q[u].D, total, o);
-            }
-        }
-        return;
-    }
-    // items with a slot over 1 KiB: frame by frame, wave-uniform
-    for (int j = 0; j < 64; ++j) {
-        const uint64_t nbj = (uint32_t)__builtin_amdgcn_readlane((int)nb, j);
-        if (nbj == 0) continue;
-        const uint64_t runj = __shfl(run, j, 64), srcj = __shfl(src, j, 64);
-        const uint64_t lenj = (uint32_t)__builtin_amdgcn_readlane((int)len, j);
-        const uint32_t kj = (uint32_t)__shfl((int)key, j, 64);
-        const uint32_t ph = (uint32_t)(srcj & 15u);
-        for (uint64_t c0 = 0; c0 < nbj; c0 += 64 * 16 * kUnroll) {
-            uint4 A[kUnroll], E[kUnroll];
-            uint32_t need[kUnroll];
-            bool nl[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const uint64_t k0 = c0 + (uint64_t)u * 1024 + 16 * lane;
-                need[u] = k0 < lenj ? (uint32_t)(lenj - k0 < 16 ? lenj - k0 : 16) : 0u;
-                nl[u] = lane != 63 && k0 + 16 < lenj;
-                const uint64_t s = srcj + k0;
-                A[u] = need[u] ? ld16(wire + (s & ~uint64_t(15))) : z;
-                E[u] = need[u] && ph && !nl[u] && ph + need[u] > 16 ? ld16(wire + (s & ~uint64_t(15)) + 16) : z;
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const uint4 nb4 = from_next_lane(A[u], E[u]);
-                const uint64_t k0 = c0 + (uint64_t)u * 1024 + 16 * lane;
-                if (k0 >= nbj) continue;
-                uint4 o = z;
-                if (need[u]) {
-                    o = ph ? funnel16(A[u], nl[u] ? nb4 : E[u], ph) : A[u];
-                    xor4(o, kj);
-                    if (need[u] < 16) o = and4(o, byte_range(0, need[u]));
-                }
-                fused_store(out, runj + k0, total, o);
-            }
-        }
-    }
-}
 
 // deserialize_plan_reduce_kernel + deserialize_plan_apply_kernel in one
 // launch, without reassembly (its control-frame pass starts at the data
@@ -624,15 +501,6 @@ __device__ __forceinline__ void fused_item(const uint8_t* __restrict__ wire, uin
 // capacity rule's status) once the offsets are known. kCopy: the fused
 // deserialize (above): each block then copies its frames into `out`; no
 // offsets or region map are written (no execute follows).
-// One unaligned 16-byte load (the part's unaligned access mode): the
-// receive plan's header loads.
-__device__ __forceinline__ uint4 ld16u(const uint8_t* p)
-{
-    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-    const u32x4u v = *reinterpret_cast<const u32x4u*>(p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
 #ifndef CFWS_FUSED_ITEMS
 #define CFWS_FUSED_ITEMS 2
 #endif
@@ -800,469 +668,6 @@ uint64_t fused_avg_max()
 {
     static const uint64_t v = (uint64_t)env_knob("CFWS_FUSED_AVG_MAX", 512);
     return v;
-}
-
-// ---------------------------------------------------------------------------
-// fixed payload slots (cfws_deserialize_slots)
-// ---------------------------------------------------------------------------
-// Frame i's payload goes to slot i (payload_off = i * slot): no prefix, so
-// no look-back, and the pass reads each wire line once. The packed receive
-// cannot: a frame's destination needs every earlier header, so its header
-// line is fetched by the parse and again by the copy (§9: 6.86 GB per
-// 16 M x 256 B launch against 4.43 GB of wire).
-//
-// Slots of at most kSlotWindow8Max bytes (deserialize_slots_window_kernel):
-// a frame's window is the 16-byte block holding its first byte and the
-// G - 1 after it, G = slot / 16 + 2 (block phase <= 15 plus header <= 14 plus
-// payload <= slot bytes), one block per virtual lane. S sub-windows of 64
-// lanes give 64 S virtual lanes (S = 1 up to 992 B -- 2 for 496-640 B, three
-// frames to a pair --, 2 up to 2,016 B, 4 up to 4,064 B, 8 up to 8,160 B),
-// so P = 64 S / G frames share a wave-round. A wave takes R rounds (R P <=
-// 64 frames) per iteration: lane l loads frame l's index, every round's
-// window blocks are issued at once together with each frame's 16 header
-// bytes (one unaligned load, lane = frame: the same lines as the windows, in
-// flight together, so HBM sees them once), each lane parses its frame and
-// writes its descriptor and status (consecutive lanes, consecutive
-// entries), and each round then takes its frames' (length, phase + header,
-// key) from the parsing lanes. A virtual lane's 16 payload bytes start
-// (phase + header) bytes into its own block: blocks c and c + 1, or c + 1
-// and c + 2 past 16 (DPP shifts by one lane, no LDS; a sub-window's last two
-// lanes take the next sub-window's first two blocks), funnelled and
-// unmasked (each chunk starts at a payload index that is a multiple of 16:
-// no key rotation). Blocks at or past the wire's end are not loaded. The
-// first form parsed in every lane of every round (480 instructions per 3
-// frames at 256 B) and ran at 5.2 TB/s.
-constexpr uint64_t kSlotWindow8Max = 512 * 16 - 32;   // eight blocks per lane up to 8,160 B
-// Rounds per iteration (their loads in flight together): 8 for one frame per
-// round (slots over 480 B), 4 for more (16 M x 256 B receive 1.686 -> 1.620
-// ms; 12 or 16 rounds: 3.3 ms; 8 M x 512 B at 4 rounds 1.59 -> 1.76 ms).
-#ifndef CFWS_SLOT_ROUNDS
-#define CFWS_SLOT_ROUNDS 8
-#endif
-#ifndef CFWS_SLOT_ROUNDS_MULTI
-#define CFWS_SLOT_ROUNDS_MULTI 4
-#endif
-#ifndef CFWS_SLOT_ROUNDS2
-#define CFWS_SLOT_ROUNDS2 4      // two blocks per lane (1,008-2,016 B): 2,016 B 2 / 4 / 6 -> 1.61-1.62 / 1.61 / 1.63 ms
-#endif
-#ifndef CFWS_SLOT_ROUNDS8
-#define CFWS_SLOT_ROUNDS8 1      // eight blocks per lane (4,080-8,160 B)
-#endif
-#ifndef CFWS_SLOT_ROUNDS4
-#define CFWS_SLOT_ROUNDS4 1      // four blocks per lane (2,032-4,064 B): 3 KiB 1 / 2 / 4 -> 1.48 / 1.55 / 1.59 ms
-#endif
-
-__device__ __forceinline__ uint4 shfl16(uint4 v, int src)
-{
-    return make_uint4((uint32_t)__shfl((int)v.x, src, 64), (uint32_t)__shfl((int)v.y, src, 64),
-                      (uint32_t)__shfl((int)v.z, src, 64), (uint32_t)__shfl((int)v.w, src, 64));
-}
-
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
-{
-    return (uint64_t)__shfl((long long)v, src, 64);
-}
-
-// The slot rule: a COMPLETE frame whose non-empty payload is longer than the
-// slot, or ends past the capacity, gets CFWS_ERROR_OUT_OF_MEMORY (the
-// reference's failed allocation, co_ws_frame.c:216-223); its slot is not
-// written.
-__device__ __forceinline__ int32_t slot_rule(int32_t st, uint64_t run, uint64_t ps, uint64_t slot, uint64_t cap)
-{
-    return st == CFWS_PARSE_COMPLETE && ps > 0 && (ps > slot || run > cap || ps > cap - run)
-               ? CFWS_ERROR_OUT_OF_MEMORY : st;
-}
-
-// The scatter form (cfws_deserialize_scatter): frame i's payload at the
-// caller's dst[i] instead of i * slot, which must be a multiple of 16 (the
-// copy stores whole aligned blocks); a frame whose offset is not does not
-// fit either.
-__device__ __forceinline__ int32_t scatter_rule(int32_t st, uint64_t run, uint64_t ps, uint64_t slot, uint64_t cap)
-{
-    st = slot_rule(st, run, ps, slot, cap);
-    return st == CFWS_PARSE_COMPLETE && ps > 0 && (run & 15u) ? CFWS_ERROR_OUT_OF_MEMORY : st;
-}
-
-__device__ __forceinline__ void slot_desc(cfws_frame_desc_t* desc, int32_t* status, uint64_t f, uint64_t run,
-                                          const cfws_frame_desc_t& d, int32_t st)
-{
-    uint4* q = reinterpret_cast<uint4*>(desc + f);
-    const uint64_t w3 = (uint64_t)d.mask_key | (uint64_t)d.fin << 32 | (uint64_t)d.opcode << 40 |
-                        (uint64_t)d.mask << 48 | (uint64_t)d.header_size << 56;
-    q[0] = make_uint4((uint32_t)run, (uint32_t)(run >> 32), (uint32_t)d.wire_off, (uint32_t)(d.wire_off >> 32));
-    q[1] = make_uint4((uint32_t)d.payload_size, (uint32_t)(d.payload_size >> 32), (uint32_t)w3,
-                      (uint32_t)(w3 >> 32));
-    status[f] = st;
-}
-
-// The compact per-frame output (cfws_deserialize_slots_info /
-// _scatter_info): the reference frame's header fields and the status in 8
-// bytes, one u64 store per frame (consecutive lanes, consecutive entries).
-__device__ __forceinline__ void slot_info(cfws_frame_info_t* info, uint64_t f, const cfws_frame_desc_t& d, int32_t st)
-{
-    const uint32_t ps = d.payload_size > 0xffffffffull ? 0xffffffffu : (uint32_t)d.payload_size;
-    const uint32_t w1 = (uint32_t)d.fin | (uint32_t)d.opcode << 8 | ((uint32_t)st & 0xffffu) << 16;
-    reinterpret_cast<uint2*>(info)[f] = make_uint2(ps, w1);
-}
-
-// the uniform receive's check: lanes whose frame is not a COMPLETE frame of
-// exactly `stride` wire bytes, one atomic per wave that has any
-__device__ __forceinline__ void count_mismatch(uint32_t* mismatch, bool odd, uint32_t lane)
-{
-    const uint64_t b = __ballot(odd);
-    if (b && lane == 0) atomicAdd(mismatch, (uint32_t)__popcll(b));
-}
-
-// kInfo: write cfws_frame_info_t entries to `info` instead of descriptors
-// and statuses; index null: frame i starts at i * stride and `mismatch`
-// (when not null) counts the frames that are not uniform frames
-template <int kSlotRounds, int kSub, bool kScatter, bool kInfo>
-__global__ void __launch_bounds__(kThreads)
-deserialize_slots_window_kernel(const uint8_t* __restrict__ wire, uint64_t wire_size,
-                                const uint64_t* __restrict__ index, uint64_t n, uint64_t max_payload,
-                                uint64_t slot, uint32_t G, cfws_frame_desc_t* __restrict__ desc,
-                                int32_t* __restrict__ status, uint8_t* __restrict__ out, uint64_t capacity,
-                                uint64_t* __restrict__ user_total, const uint64_t* __restrict__ dst,
-                                cfws_frame_info_t* __restrict__ infos, uint64_t stride,
-                                uint32_t* __restrict__ mismatch)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    // kSub sub-windows of 64 lanes make 64 kSub virtual lanes, v = 64 sw +
-    // lane; frame g of a round takes virtual lanes [g G, g G + G), P = 64 kSub
-    // / G frames, so lane `lane` of sub-window sw holds block c[sw] of the
-    // round's frame g[sw]
-    const uint32_t P = 64u * kSub / G;
-    uint32_t g[kSub], c[kSub];
-#pragma unroll
-    for (int sw = 0; sw < kSub; ++sw) {
-        g[sw] = (64u * sw + lane) / G;
-        c[sw] = 64u * sw + lane - g[sw] * G;
-    }
-    const uint32_t R = P * kSlotRounds <= 64 ? (uint32_t)kSlotRounds : 64u / P;
-    const uint64_t FI = uint64_t(R) * P;                 // frames per wave-iteration
-    const uint64_t grid_frames = uint64_t(gridDim.x) * kWaves * FI;
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    const bool b16 = wire_size >= 16;
-    const uint64_t lastu = wire_size - 16;
-    for (uint64_t f0 = (uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6)) * FI; f0 < n; f0 += grid_frames) {
-        const uint64_t fl = f0 + lane;
-        const bool mine = lane < FI && fl < n;
-        // the frame's start: the index, or frame i at i * stride (the uniform
-        // receive: its window loads need no index load before them)
-        const uint64_t wl = !mine ? ~uint64_t(0) : index ? index[fl] : fl * stride;
-        // the frame's payload offset: its slot, or the caller's (scatter)
-        const uint64_t runl = !mine ? 0 : kScatter ? dst[fl] : fl * slot;
-        // every round's window block, then each frame's header bytes
-        uint4 A[kSlotRounds][kSub];
-#pragma unroll
-        for (int u = 0; u < kSlotRounds; ++u) {
-#pragma unroll
-            for (int sw = 0; sw < kSub; ++sw) {
-                const uint32_t src = (uint32_t)u * P + g[sw];
-                const uint64_t wo = shfl64(wl, (int)(src < 64 ? src : 63));
-                const uint64_t blk = (wo & ~uint64_t(15)) + 16ull * c[sw];   // block c of the window
-                A[u][sw] = (uint32_t)u < R && g[sw] < P && wo < wire_size && blk < wire_size
-                               ? ld16(wire + blk) : z;
-            }
-        }
-        const uint4 hw = mine && b16 && wl <= lastu ? ld16u(wire + wl) : z;
-        // lane l parses frame f0 + l; its round info: payload length (<= slot
-        // < 2^16) | (phase + header size) << 16, zero when not copied
-        uint32_t info = 0, key = 0;
-        bool odd = false;   // not a uniform frame at its place (mismatch count)
-        if (mine) {
-            cfws_frame_desc_t d;
-            int32_t st;
-            if (b16 && wl <= lastu) {
-                const uint32_t w[4] = {hw.x, hw.y, hw.z, hw.w};
-                st = parse_ws_header_regs(w, wire_size - wl, max_payload, d);
-                d.wire_off = wl;
-            } else {
-                st = parse_ws_header(wire, wire_size, wl, max_payload, d);
-            }
-            const uint64_t run = runl;
-            st = kScatter ? scatter_rule(st, run, d.payload_size, slot, capacity)
-                          : slot_rule(st, run, d.payload_size, slot, capacity);
-            if constexpr (kInfo)
-                slot_info(infos, fl, d, st);
-            else
-                slot_desc(desc, status, fl, run, d, st);
-            if (fl == n - 1 && user_total) {
-                const uint64_t t = n * slot;
-                *user_total = t < capacity ? t : capacity;
-            }
-            if (st == CFWS_PARSE_COMPLETE && d.payload_size > 0)
-                info = (uint32_t)d.payload_size | ((uint32_t)(wl & 15u) + d.header_size) << 16;
-            key = d.mask ? d.mask_key : 0u;
-            odd = st != CFWS_PARSE_COMPLETE || d.header_size + d.payload_size != stride;
-        }
-        if (mismatch) count_mismatch(mismatch, odd, lane);
-#pragma unroll
-        for (int u = 0; u < kSlotRounds; ++u) {
-            if ((uint32_t)u >= R) break;   // wave-uniform
-#pragma unroll
-            for (int sw = 0; sw < kSub; ++sw) {
-                const uint32_t src = (uint32_t)u * P + g[sw];
-                const int s = (int)(src < 64 ? src : 63);
-                const uint32_t inf = (uint32_t)__shfl((int)info, s, 64);
-                const uint32_t k = (uint32_t)__shfl((int)key, s, 64);
-                const uint32_t len = inf & 0xffffu, off = inf >> 16;
-                const uint64_t runf = kScatter ? shfl64(runl, s) : (f0 + src) * slot;
-                // blocks c + 1 and c + 2 of this sub-window, by DPP (every
-                // lane); lanes 62 and 63 of a sub-window take the next one's
-                // first two blocks
-                const uint4 l0 = sw + 1 < kSub ? shfl16(A[u][sw + 1 < kSub ? sw + 1 : sw], 0) : z;
-                const uint4 l1 = sw + 1 < kSub ? shfl16(A[u][sw + 1 < kSub ? sw + 1 : sw], 1) : z;
-                const uint4 n1 = from_next_lane(A[u][sw], l0);
-                const uint4 n2 = from_next_lane(n1, l1);
-                const uint32_t q = c[sw];          // payload chunk
-                if (g[sw] < P && 16u * q < len) {
-                    const bool k1 = off >= 16;
-                    const uint4 B0 = k1 ? n1 : A[u][sw], B1 = k1 ? n2 : n1;
-                    const uint32_t sh = off & 15u;
-                    uint4 o = sh ? funnel16(B0, B1, sh) : B0;
-                    xor4(o, k);
-                    if (len - 16u * q < 16u) o = and4(o, byte_range(0, len - 16u * q));
-                    fused_store(out, runf + 16ull * q, capacity, o);
-                }
-            }
-        }
-    }
-}
-
-#ifndef CFWS_SLOT_UNROLL
-#define CFWS_SLOT_UNROLL 16      // slots over 8,160 B: 64 K x 64 KiB receive 2.04 / 1.76 / 1.71 ms at 4 / 8 / 16 rounds, 8 KiB 1.72 at each
-#endif
-constexpr int kSlotUnroll = CFWS_SLOT_UNROLL;   // deserialize_slots_kernel: rounds of loads in flight
-
-// Slots over kSlotWindow8Max: one frame per thread parsed (its header line
-// fetched twice, a small share of a frame this long), the payloads copied
-// by fused_item.
-template <bool kScatter, bool kInfo>
-__global__ void __launch_bounds__(kThreads)
-deserialize_slots_kernel(const uint8_t* __restrict__ wire, uint64_t wire_size, const uint64_t* __restrict__ index,
-                         uint64_t n, uint64_t max_payload, uint64_t slot, cfws_frame_desc_t* __restrict__ desc,
-                         int32_t* __restrict__ status, uint8_t* __restrict__ out, uint64_t capacity,
-                         uint64_t* __restrict__ user_total, const uint64_t* __restrict__ dst,
-                         cfws_frame_info_t* __restrict__ info, uint64_t stride, uint32_t* __restrict__ mismatch)
-{
-    const uint64_t f = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-    uint64_t run = 0, src = 0;
-    uint32_t len = 0, nb = 0, key = 0;
-    bool odd = false;
-    if (f < n) {
-        cfws_frame_desc_t d;
-        const uint64_t s0 = index ? index[f] : f * stride;
-        run = kScatter ? dst[f] : f * slot;
-        const int32_t p = parse_ws_header(wire, wire_size, s0, max_payload, d);
-        const int32_t st = kScatter ? scatter_rule(p, run, d.payload_size, slot, capacity)
-                                    : slot_rule(p, run, d.payload_size, slot, capacity);
-        if constexpr (kInfo)
-            slot_info(info, f, d, st);
-        else
-            slot_desc(desc, status, f, run, d, st);
-        if (st == CFWS_PARSE_COMPLETE) {
-            len = (uint32_t)d.payload_size;   // <= slot < 2^31
-            nb = (len + 15u) & ~15u;
-            src = s0 + d.header_size;
-            key = d.mask ? d.mask_key : 0u;
-        }
-        odd = st != CFWS_PARSE_COMPLETE || d.header_size + d.payload_size != stride;
-        if (f == n - 1 && user_total) {
-            const uint64_t t = n * slot;
-            *user_total = t < capacity ? t : capacity;
-        }
-    }
-    if (mismatch) count_mismatch(mismatch, odd, threadIdx.x & 63u);
-    fused_item<kSlotUnroll>(wire, out, capacity, run, src, len, nb, key, threadIdx.x & 63u);
-}
-
-// Slots over kSlotWindow8Max, piece by piece: wave w copies piece w % P of
-// frame w / P (kSlotPiece bytes of slot), so a 64 KiB frame is 32 waves'
-// work and a launch has n x P waves. P is the slot's piece count; when the
-// batch's frames are shorter on average (wire bytes / frames) P is that
-// average's piece count and each wave takes pieces w % P, w % P + P, ...
-// (kLoop), so a large slot holding short payloads does not cost a wave per
-// piece of the slot. Batches averaging under one piece per frame take the
-// per-frame kernel, which packs short frames into shared wave-instructions
-// (slots_route; tools/slot_sparse_probe.py: 1 M x 256 B in 16 KiB slots
-// 0.13 ms there against 0.59 one wave per frame). The per-frame kernel above
-// gives each wave the 64 frames its lanes parsed, one after another: 1,024
-// waves for 64 K frames, one per SIMD. Every wave of a frame parses its
-// header (one line, the same address in every lane); piece 0's lane 0 writes
-// the frame's descriptor + status or info entry and counts a mismatch.
-// 64 K x 64 KiB receive (profiles/r06/compact/slot_pieces/): per-frame
-// kernel 1.59-1.64 ms; pieces of 8 / 4 / 2 / 1 KiB 1.51-1.60 / 1.42-1.49 /
-// 1.35-1.36 / 2.13 ms; 2 KiB with write-through stores 1.31-1.32 (8 KiB
-// frames 1.38, against 1.51-1.64).
-#ifndef CFWS_SLOT_PIECE_AUX
-#define CFWS_SLOT_PIECE_AUX 19        // write-through (sc0 sc1 nt), as the WS receive; 0: the global nt store
-#endif
-#ifndef CFWS_SLOT_PIECE_UNROLL
-#define CFWS_SLOT_PIECE_UNROLL 2
-#endif
-constexpr int kSlotPieceUnroll = CFWS_SLOT_PIECE_UNROLL;            // rounds of loads in flight per wave
-constexpr uint64_t kSlotPiece = 64ull * 16 * kSlotPieceUnroll;     // 2 KiB
-template <bool kScatter, bool kInfo, bool kLoop>
-__global__ void __launch_bounds__(kThreads)
-deserialize_slots_piece_kernel(const uint8_t* __restrict__ wire, uint64_t wire_size,
-                               const uint64_t* __restrict__ index, uint64_t n, uint64_t max_payload, uint64_t slot,
-                               cfws_frame_desc_t* __restrict__ desc, int32_t* __restrict__ status,
-                               uint8_t* __restrict__ out, uint64_t capacity, uint64_t* __restrict__ user_total,
-                               const uint64_t* __restrict__ dst, cfws_frame_info_t* __restrict__ info,
-                               uint64_t stride, uint32_t* __restrict__ mismatch, uint64_t pieces)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    const uint64_t waves = n * pieces;
-    for (uint64_t w = uint64_t(blockIdx.x) * kWaves + wv; w < waves; w += uint64_t(gridDim.x) * kWaves) {
-        const uint64_t f = w / pieces, piece = w - f * pieces;
-        cfws_frame_desc_t d;
-        const uint64_t s0 = index ? index[f] : f * stride;
-        const uint64_t run = kScatter ? dst[f] : f * slot;
-        const int32_t p = parse_ws_header(wire, wire_size, s0, max_payload, d);
-        const int32_t st = kScatter ? scatter_rule(p, run, d.payload_size, slot, capacity)
-                                    : slot_rule(p, run, d.payload_size, slot, capacity);
-        if (piece == 0 && lane == 0) {
-            if constexpr (kInfo)
-                slot_info(info, f, d, st);
-            else
-                slot_desc(desc, status, f, run, d, st);
-            if (f == n - 1 && user_total) {
-                const uint64_t t = n * slot;
-                *user_total = t < capacity ? t : capacity;
-            }
-            if (mismatch && (st != CFWS_PARSE_COMPLETE || d.header_size + d.payload_size != stride))
-                atomicAdd(mismatch, 1u);
-        }
-        if (st != CFWS_PARSE_COMPLETE) continue;             // wave-uniform: every lane parsed the same frame
-        const uint64_t len = d.payload_size;                 // <= slot <= 2^31
-        const uint64_t nb = (len + 15) & ~uint64_t(15);
-        const uint64_t src = s0 + d.header_size;
-        const uint32_t key = d.mask ? d.mask_key : 0u;
-        const uint32_t ph = (uint32_t)(src & 15u);
-        // this wave's piece of the frame (kLoop: pieces piece, piece + P, ...;
-        // without, the loop body once: the straight-line form measured 7 %
-        // faster when every frame fills its slot)
-        for (uint64_t c0 = piece * kSlotPiece; c0 < nb; c0 += pieces * kSlotPiece) {
-            const auto prs = __builtin_amdgcn_make_buffer_rsrc(out + run + c0, 0, (int)kSlotPiece, 0x00020000);
-            uint4 A[kSlotPieceUnroll], E[kSlotPieceUnroll];
-            uint32_t need[kSlotPieceUnroll];
-            bool nl[kSlotPieceUnroll];
-#pragma unroll
-            for (int u = 0; u < kSlotPieceUnroll; ++u) {
-                const uint64_t k0 = c0 + (uint64_t)u * 1024 + 16 * lane;
-                need[u] = k0 < len ? (uint32_t)(len - k0 < 16 ? len - k0 : 16) : 0u;
-                nl[u] = lane != 63 && k0 + 16 < len;                 // the next lane loads the next block
-                const uint64_t s = src + k0;
-                A[u] = need[u] ? ld16(wire + (s & ~uint64_t(15))) : z;
-                E[u] = need[u] && ph && !nl[u] && ph + need[u] > 16 ? ld16(wire + (s & ~uint64_t(15)) + 16) : z;
-            }
-#pragma unroll
-            for (int u = 0; u < kSlotPieceUnroll; ++u) {
-                const uint4 nb4 = from_next_lane(A[u], E[u]);       // every lane: DPP needs the full wave
-                const uint64_t k0 = c0 + (uint64_t)u * 1024 + 16 * lane;
-                if (k0 >= nb) continue;
-                uint4 o = z;
-                if (need[u]) {
-                    o = ph ? funnel16(A[u], nl[u] ? nb4 : E[u], ph) : A[u];
-                    xor4(o, key);
-                    if (need[u] < 16) o = and4(o, byte_range(0, need[u]));
-                }
-                if (CFWS_SLOT_PIECE_AUX != 0 && run + k0 + 16 <= capacity) {
-                    // a buffer store over the wave's piece (cache policy CFWS_SLOT_PIECE_AUX)
-                    const u32x4 v = {o.x, o.y, o.z, o.w};
-                    __builtin_amdgcn_raw_buffer_store_b128(v, prs, (int)(k0 - c0), 0, CFWS_SLOT_PIECE_AUX);
-                } else {
-                    fused_store(out, run + k0, capacity, o);
-                }
-            }
-            if (!kLoop) break;
-        }
-    }
-}
-
-// Frames of at least CFWS_SLOT_SUB2_G lanes (default 33: slots of 496
-// bytes and more) that fit three to a 128-lane pair of sub-windows (up to
-// 42 lanes: slots up to 640 bytes) pack two sub-windows per round instead of
-// one frame per round. Receive, two sub-windows against one: 512 B 1.535 ->
-// 1.498 ms; 768 B (two frames per pair) 1.447 -> 1.490; 256 B and 384 B
-// (already 2-3 frames per sub-window) 1.508 -> 1.552, 1.473 -> 1.506
-// (profiles/r05/slots/sub2_ab/). A/B knob; 65 turns the packing off.
-uint32_t slot_sub2_g()
-{
-    static const uint32_t v = (uint32_t)env_knob("CFWS_SLOT_SUB2_G", 33);
-    return v;
-}
-
-// The receive without an index (cfws_deserialize_slots_uniform) keeps one
-// frame per round there: with no index load ahead of the window loads, 8 M
-// x 512 B takes 1.50 ms at one sub-window against 1.62 at two
-// (profiles/r06/compact/implicit/). A/B knob.
-uint32_t slot_sub2_g_implicit()
-{
-    static const uint32_t v = (uint32_t)env_knob("CFWS_SLOT_SUB2_G_IMPLICIT", 65);
-    return v;
-}
-
-// The same for four sub-windows: frames of CFWS_SLOT_SUB4_G (default 129:
-// off) to 85 lanes, three to 256 virtual lanes (A/B knob)
-uint32_t slot_sub4_g()
-{
-    static const uint32_t v = (uint32_t)env_knob("CFWS_SLOT_SUB4_G", 129);
-    return v;
-}
-
-bool slots_window()
-{
-    static const bool v = env_knob("CFWS_SLOTS_WINDOW", 1) != 0;
-    return v;
-}
-
-bool slots_piece()
-{
-    static const bool v = env_knob("CFWS_SLOTS_PIECE", 1) != 0;
-    return v;
-}
-
-// the kernel a slot / scatter receive takes (slots_impl and
-// cfws_deserialize_slots_pass_kernel): windows up to kSlotWindow8Max-byte
-// slots, pieces past that (A/B knobs: CFWS_SLOTS_WINDOW=0, CFWS_SLOTS_PIECE=0
-// fall back to the per-frame kernel)
-enum SlotsRoute { kSlotsWindow, kSlotsPiece, kSlotsPerFrame };
-// Slots of 2 KiB up to kSlotWindow8Max take pieces too where the pieces'
-// lanes are at least 85 % used and every piece starts on a 128-byte line.
-// Receive without / with an index (profiles/r06/compact/slot_pieces/):
-// 2 / 4 / 6 / 7.5 KiB 1.41 / 1.38 / 1.36 / 1.45 and 1.47 / 1.43 / 1.40 /
-// 1.47 ms against the windows' 1.59 / 1.58 / 1.54 / 1.57 and 1.84 / 1.62 /
-// 1.52 / 1.51; 5 KiB (83 % used) 1.47 / 1.56 against 1.52 / 1.53; 2.5 / 3 KiB
-// (63 / 75 %) 1.90 / 1.62 against 1.52 / 1.48; 8,160 B (off the 128-byte
-// lines) 1.86 against 1.69.
-bool piece_pays(uint64_t slot)
-{
-    const uint64_t pieces = (slot + kSlotPiece - 1) / kSlotPiece;
-    return slot % 128 == 0 && 20 * slot >= 17 * pieces * kSlotPiece;
-}
-
-SlotsRoute slots_route(uint64_t slot, uint64_t n, uint64_t wire_size)
-{
-    static const uint64_t piece_min = (uint64_t)env_knob("CFWS_SLOTS_PIECE_MIN", 2048);   // A/B knob
-    // the batch's average frame (wire bytes): pieces pay for frames that
-    // fill them, not for short frames in large slots
-    const uint64_t avg = n ? wire_size / n : 0;
-    const bool piece = slots_piece() && slot >= piece_min &&
-                       (slot > kSlotWindow8Max ? avg > 1040 : piece_pays(slot) && 20 * avg >= 17 * slot);
-    // a window spans the whole slot, whatever the frame: frames of up to
-    // 1 KiB filling under half their slot (under 80 % of a slot of 1 KiB or
-    // more) take the per-frame kernel, which packs them into shared
-    // wave-instructions (tools/slot_sparse_probe.py: 256 B frames in 4 KiB
-    // slots 0.14 against 1.15 ms, 512 B in 1 KiB 0.91 against 1.25, 768 B in
-    // 1 KiB 1.30 against 1.41; 128 B in 256 B slots stay on the windows,
-    // 0.67 against 0.71)
-    const bool sparse = avg <= 1040 && (2 * avg < slot || (slot >= 1024 && 5 * avg < 4 * slot));
-    if (slot <= kSlotWindow8Max && slots_window() && !piece && !sparse) return kSlotsWindow;
-    return piece ? kSlotsPiece : kSlotsPerFrame;
 }
 
 // Single-pass plans above kSelfScanBlocks blocks (CFWS_PLAN_SINGLE=0: the
@@ -1830,205 +1235,7 @@ int cfws_deserialize_batch(const void* d_wire, uint64_t wire_size, const uint64_
 
 }  // extern "C"
 
-namespace {
-
-// cfws_deserialize_slots (dst null: frame i at i * slot) and
-// cfws_deserialize_scatter (frame i at dst[i], slot = the largest payload
-// a frame may have)
-int slots_impl(const void* d_wire, uint64_t wire_size, const uint64_t* d_index, const uint64_t* dst, size_t n,
-               uint64_t max_payload, uint64_t slot, cfws_frame_desc_t* d_desc, int32_t* d_status,
-               void* d_payload, uint64_t cap, uint64_t* d_total, void* stream, bool scatter, const char* what,
-               cfws_frame_info_t* d_info = nullptr, uint64_t stride = 0, uint32_t* d_mismatch = nullptr)
-{
-    if (int rc = check_init()) return rc;
-    if (slot < 16 || (slot & 15) || slot > (1ull << 31))
-        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "slot bytes must be a multiple of 16 in [16, 2^31]",
-                       hipSuccess);
-    if (n > 0xffffffffull) return set_err(CFWS_ERROR_INVALID_ARGUMENT, "too many frames", hipSuccess);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0) {
-        if (d_total && hipMemsetAsync(d_total, 0, sizeof(uint64_t), st) != hipSuccess)
-            return launch_check(what);
-        return CFWS_OK;
-    }
-    const bool info = d_info != nullptr;
-    if (!d_wire || (!d_index && !stride) || (!info && (!d_desc || !d_status)) || (cap && !d_payload) ||
-        (scatter && !dst))
-        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "null pointer", hipSuccess);
-    if (misaligned(d_payload, d_wire))
-        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "arenas must be 16-byte aligned", hipSuccess);
-    const uint8_t* w = static_cast<const uint8_t*>(d_wire);
-    uint8_t* out = static_cast<uint8_t*>(d_payload);
-    const CfwsPassTimer timer(st);
-    const SlotsRoute route = slots_route(slot, n, wire_size);
-    if (route == kSlotsWindow) {
-        // one wave-iteration of R P frames per wave (CFWS_SLOT_GRID caps the
-        // workgroups: a grid-stride loop; A/B knob)
-        const uint32_t G = (uint32_t)(slot / 16 + 2);
-        const uint32_t sub2 = d_index ? slot_sub2_g() : slot_sub2_g_implicit();
-        const uint32_t S = G > 256 ? 8
-                           : G > 128 || (G >= slot_sub4_g() && 256 / G >= 3) ? 4
-                           : G > 64 || (G >= sub2 && 128 / G >= 3) ? 2 : 1;   // sub-windows
-        const uint32_t P = 64 * S / G;
-        const uint64_t RK = S == 8 ? CFWS_SLOT_ROUNDS8 : S == 4 ? CFWS_SLOT_ROUNDS4 : S == 2 ? CFWS_SLOT_ROUNDS2
-                            : P > 1 ? CFWS_SLOT_ROUNDS_MULTI : CFWS_SLOT_ROUNDS;
-        const uint64_t R = P * RK <= 64 ? RK : 64 / P;
-        const uint64_t per_block = uint64_t(kWaves) * R * P;
-        static const uint64_t cap_blocks = [] {
-            const int64_t v = env_knob("CFWS_SLOT_GRID", 0);   // 0: one iteration per wave
-            return v > 0 ? (uint64_t)v : 0x7fffffffull;
-        }();
-        const uint64_t want = (n + per_block - 1) / per_block;
-        const uint32_t grid = (uint32_t)(want < cap_blocks ? want : cap_blocks);
-        auto window = [&](auto scatter, auto compact) {
-            constexpr bool kSc = decltype(scatter)::value;
-            constexpr bool kIn = decltype(compact)::value;
-            if (S == 8)
-                deserialize_slots_window_kernel<CFWS_SLOT_ROUNDS8, 8, kSc, kIn><<<grid, kThreads, 0, st>>>(
-                    w, wire_size, d_index, n, max_payload, slot, G, d_desc, d_status, out, cap, d_total, dst, d_info,
-                    stride, d_mismatch);
-            else if (S == 4)
-                deserialize_slots_window_kernel<CFWS_SLOT_ROUNDS4, 4, kSc, kIn><<<grid, kThreads, 0, st>>>(
-                    w, wire_size, d_index, n, max_payload, slot, G, d_desc, d_status, out, cap, d_total, dst, d_info,
-                    stride, d_mismatch);
-            else if (S == 2)
-                deserialize_slots_window_kernel<CFWS_SLOT_ROUNDS2, 2, kSc, kIn><<<grid, kThreads, 0, st>>>(
-                    w, wire_size, d_index, n, max_payload, slot, G, d_desc, d_status, out, cap, d_total, dst, d_info,
-                    stride, d_mismatch);
-            else if (P > 1)
-                deserialize_slots_window_kernel<CFWS_SLOT_ROUNDS_MULTI, 1, kSc, kIn><<<grid, kThreads, 0, st>>>(
-                    w, wire_size, d_index, n, max_payload, slot, G, d_desc, d_status, out, cap, d_total, dst, d_info,
-                    stride, d_mismatch);
-            else
-                deserialize_slots_window_kernel<CFWS_SLOT_ROUNDS, 1, kSc, kIn><<<grid, kThreads, 0, st>>>(
-                    w, wire_size, d_index, n, max_payload, slot, G, d_desc, d_status, out, cap, d_total, dst, d_info,
-                    stride, d_mismatch);
-        };
-        // the scatter form as its own instantiation: its per-round offset
-        // shuffle, as a run-time branch in one kernel, cost the 1 KiB slot
-        // receive 11 % (1.525 -> 1.70 ms)
-        if (scatter && info)
-            window(std::true_type{}, std::true_type{});
-        else if (scatter)
-            window(std::true_type{}, std::false_type{});
-        else if (info)
-            window(std::false_type{}, std::true_type{});
-        else
-            window(std::false_type{}, std::false_type{});
-    } else if (route == kSlotsPiece) {
-        // waves per frame: the slot's pieces, at most the pieces of the
-        // batch's average frame (its wire bytes; at least one)
-        const uint64_t slot_pieces = (slot + kSlotPiece - 1) / kSlotPiece;
-        const uint64_t avg_pieces = (wire_size / n + kSlotPiece - 1) / kSlotPiece;
-        const uint64_t pieces = avg_pieces < 1 ? 1 : avg_pieces < slot_pieces ? avg_pieces : slot_pieces;
-        const bool loop = pieces < slot_pieces;
-        const uint64_t waves = n * pieces;
-        const uint64_t want = (waves + kWaves - 1) / kWaves;
-        const uint32_t grid = (uint32_t)(want < (1u << 22) ? want : (1u << 22));   // a grid-stride loop past that
-        auto piecewise = [&](auto scatter, auto compact) {
-            constexpr bool kSc = decltype(scatter)::value, kIn = decltype(compact)::value;
-            if (loop)
-                deserialize_slots_piece_kernel<kSc, kIn, true><<<grid, kThreads, 0, st>>>(
-                    w, wire_size, d_index, n, max_payload, slot, d_desc, d_status, out, cap, d_total, dst, d_info,
-                    stride, d_mismatch, pieces);
-            else
-                deserialize_slots_piece_kernel<kSc, kIn, false><<<grid, kThreads, 0, st>>>(
-                    w, wire_size, d_index, n, max_payload, slot, d_desc, d_status, out, cap, d_total, dst, d_info,
-                    stride, d_mismatch, pieces);
-        };
-        if (scatter && info)
-            piecewise(std::true_type{}, std::true_type{});
-        else if (scatter)
-            piecewise(std::true_type{}, std::false_type{});
-        else if (info)
-            piecewise(std::false_type{}, std::true_type{});
-        else
-            piecewise(std::false_type{}, std::false_type{});
-    } else {
-        auto one = [&](auto scatter, auto compact) {
-            deserialize_slots_kernel<decltype(scatter)::value, decltype(compact)::value>
-                <<<grid_for(n, kThreads), kThreads, 0, st>>>(w, wire_size, d_index, n, max_payload, slot, d_desc,
-                                                             d_status, out, cap, d_total, dst, d_info, stride,
-                                                             d_mismatch);
-        };
-        if (scatter && info)
-            one(std::true_type{}, std::true_type{});
-        else if (scatter)
-            one(std::true_type{}, std::false_type{});
-        else if (info)
-            one(std::false_type{}, std::true_type{});
-        else
-            one(std::false_type{}, std::false_type{});
-    }
-    return launch_check(what);
-}
-
-}  // namespace
-
 extern "C" {
-
-int cfws_deserialize_slots(const void* d_wire, uint64_t wire_size, const uint64_t* d_index, size_t n,
-                           uint64_t max_payload, uint64_t slot, cfws_frame_desc_t* d_desc, int32_t* d_status,
-                           void* d_payload, uint64_t cap, uint64_t* d_total, void* stream)
-{
-    const CfwsPassScope pass_scope;
-    return slots_impl(d_wire, wire_size, d_index, nullptr, n, max_payload, slot, d_desc, d_status, d_payload, cap,
-                      d_total, stream, false, "deserialize_slots");
-}
-
-int cfws_deserialize_scatter(const void* d_wire, uint64_t wire_size, const uint64_t* d_index,
-                             const uint64_t* d_payload_off, size_t n, uint64_t max_payload, uint64_t max_slot,
-                             cfws_frame_desc_t* d_desc, int32_t* d_status, void* d_payload, uint64_t cap,
-                             void* stream)
-{
-    const CfwsPassScope pass_scope;
-    return slots_impl(d_wire, wire_size, d_index, d_payload_off, n, max_payload, max_slot, d_desc, d_status,
-                      d_payload, cap, nullptr, stream, true, "deserialize_scatter");
-}
-
-int cfws_deserialize_slots_info(const void* d_wire, uint64_t wire_size, const uint64_t* d_index, size_t n,
-                                uint64_t max_payload, uint64_t slot, cfws_frame_info_t* d_info, void* d_payload,
-                                uint64_t cap, uint64_t* d_total, void* stream)
-{
-    const CfwsPassScope pass_scope;
-    if (!d_info && n) return set_err(CFWS_ERROR_INVALID_ARGUMENT, "null pointer", hipSuccess);
-    return slots_impl(d_wire, wire_size, d_index, nullptr, n, max_payload, slot, nullptr, nullptr, d_payload, cap,
-                      d_total, stream, false, "deserialize_slots_info", d_info);
-}
-
-int cfws_deserialize_scatter_info(const void* d_wire, uint64_t wire_size, const uint64_t* d_index,
-                                  const uint64_t* d_payload_off, size_t n, uint64_t max_payload, uint64_t max_slot,
-                                  cfws_frame_info_t* d_info, void* d_payload, uint64_t cap, void* stream)
-{
-    const CfwsPassScope pass_scope;
-    if (!d_info && n) return set_err(CFWS_ERROR_INVALID_ARGUMENT, "null pointer", hipSuccess);
-    return slots_impl(d_wire, wire_size, d_index, d_payload_off, n, max_payload, max_slot, nullptr, nullptr,
-                      d_payload, cap, nullptr, stream, true, "deserialize_scatter_info", d_info);
-}
-
-int cfws_deserialize_slots_uniform(const void* d_wire, uint64_t wire_size, size_t n, uint64_t stride,
-                                   uint64_t max_payload, uint64_t slot, cfws_frame_info_t* d_info, void* d_payload,
-                                   uint64_t cap, uint64_t* d_total, uint32_t* d_mismatch, void* stream)
-{
-    const CfwsPassScope pass_scope;
-    if (int rc = check_init()) return rc;
-    if (stride < 2 || (n && stride > (1ull << 63) / n))
-        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "frame stride must be >= 2 and n * stride < 2^63", hipSuccess);
-    if (!d_info && n) return set_err(CFWS_ERROR_INVALID_ARGUMENT, "null pointer", hipSuccess);
-    if (d_mismatch && hipMemsetAsync(d_mismatch, 0, sizeof(uint32_t), static_cast<hipStream_t>(stream)) != hipSuccess)
-        return launch_check("deserialize_slots_uniform");
-    return slots_impl(d_wire, wire_size, nullptr, nullptr, n, max_payload, slot, nullptr, nullptr, d_payload, cap,
-                      d_total, stream, false, "deserialize_slots_uniform", d_info, stride, d_mismatch);
-}
-
-const char* cfws_deserialize_slots_pass_kernel(size_t n, uint64_t wire_size, uint64_t slot)
-{
-    switch (slots_route(slot, n, wire_size)) {
-    case kSlotsWindow: return "deserialize_slots_window_kernel";
-    case kSlotsPiece: return "deserialize_slots_piece_kernel";
-    default: return "deserialize_slots_kernel";
-    }
-}
 
 #if CFWS_PLAN_TRACE
 // tools/plan_trace.py: the last traced launch's stamps, blocks [0, n)

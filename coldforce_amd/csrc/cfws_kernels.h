@@ -1,7 +1,8 @@
 // cfws_kernels.h -- device code and launch helpers shared by the codec's
 // translation units (cfws_device.hip: WS plan / execute / batch ABI and the
-// small-batch path; cfws_h2.hip: WebSocket over HTTP/2; cfws_ops.hip: split
-// ops, handshake keys, device indexing, copies and fills). Everything here is
+// small-batch path; cfws_slots.hip: the receive into fixed slots;
+// cfws_h2.hip: WebSocket over HTTP/2; cfws_ops.hip: split ops, handshake
+// keys, device indexing, copies and fills). Everything here is
 // internal to each unit (anonymous namespace); the error state and the
 // deserialize plan, which the units share, are defined once in
 // cfws_device.hip (namespace cfws_rt).
@@ -1490,6 +1491,170 @@ __device__ __forceinline__ int32_t parse_ws_header(const uint8_t* __restrict__ w
     const int32_t st = parse_ws_header_regs(w, avail, max_payload, d);
     d.wire_off = s;
     return st;
+}
+
+// One unaligned 16-byte load (the part's unaligned access mode): the
+// receive plans' header loads.
+__device__ __forceinline__ uint4 ld16u(const uint8_t* p)
+{
+    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
+    const u32x4u v = *reinterpret_cast<const u32x4u*>(p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// ---- a wave copies the frames its lanes parsed --------------------------------
+// The copy of the fused deserialize (cfws_device.hip) and of the slot
+// receive (cfws_slots.hip). Per item (lane l: one frame), the wave's largest
+// slot sets how many frames share one wave-instruction: groups of G lanes
+// (G x 16 bytes >= the slot), one frame per group; items with a slot over
+// 1 KiB go frame by frame, 1 KiB per instruction. A lane's chunk is its
+// frame's source block funnel-shifted with the next lane's block over DPP
+// (the lane loads the next block itself at its group's end), XORed with the
+// key (each chunk starts at a payload index that is a multiple of 16, so the
+// key needs no rotation) and masked past the payload: every slot byte below
+// the pass total is written once, payload or zero.
+#ifndef CFWS_FUSED_UNROLL
+#define CFWS_FUSED_UNROLL 4
+#endif
+constexpr int kFusedUnroll = CFWS_FUSED_UNROLL;   // rounds of loads in flight per wave
+
+__device__ __forceinline__ void fused_store(uint8_t* __restrict__ out, uint64_t D, uint64_t total, uint4 o)
+{
+    if (D + 16 <= total) {
+        st16(out + D, o);
+    } else {
+        for (uint32_t j = 0; D + j < total; ++j) {
+            const uint32_t w = j < 4 ? o.x : (j < 8 ? o.y : (j < 12 ? o.z : o.w));
+            out[D + j] = (uint8_t)(w >> (8 * (j & 3)));
+        }
+    }
+}
+
+// One lane's chunk in a round: its destination D and source s, the bytes
+// of the slot it writes (nbytes) and of those the payload (need), the key.
+struct FusedChunk {
+    uint64_t D, s;
+    uint32_t need, nbytes, key;
+};
+
+// A frame copied 1 KiB per wave-instruction (wave-uniform frame: payload of
+// `len` bytes at wire offset `src`, ph = src & 15): lane `lane`'s chunk at
+// payload byte k0 = ... + 16 lane. frame_chunk_load issues its loads: A, the
+// aligned block holding its first byte, and E, the block after it where no
+// next lane loads that (lane 63, the payload's end); need: the chunk's
+// payload bytes; nl: the next lane loads the next block. frame_chunk_value,
+// called by every lane (DPP needs the full wave), makes the 16 bytes (zeros
+// past the payload) of a lane with a chunk to write (`live`) and hands them
+// to the caller's store. (Four values, not a struct: arrays of a struct cost
+// the fused deserialize four VGPRs.)
+__device__ __forceinline__ void frame_chunk_load(const uint8_t* __restrict__ wire, uint64_t src, uint64_t len,
+                                                 uint64_t k0, uint32_t ph, uint32_t lane, uint4& A, uint4& E,
+                                                 uint32_t& need, bool& nl)
+{
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    need = k0 < len ? (uint32_t)(len - k0 < 16 ? len - k0 : 16) : 0u;
+    nl = lane != 63 && k0 + 16 < len;
+    const uint64_t s = src + k0;
+    A = need ? ld16(wire + (s & ~uint64_t(15))) : z;
+    E = need && ph && !nl && ph + need > 16 ? ld16(wire + (s & ~uint64_t(15)) + 16) : z;
+}
+
+template <typename Store>
+__device__ __forceinline__ void frame_chunk_value(const uint4& A, const uint4& E, uint32_t need, bool nl, uint32_t ph,
+                                                  uint32_t key, bool live, Store&& store)
+{
+    const uint4 nb4 = from_next_lane(A, E);
+    if (!live) return;
+    uint4 o = make_uint4(0, 0, 0, 0);
+    if (need) {
+        o = ph ? funnel16(A, nl ? nb4 : E, ph) : A;
+        xor4(o, key);
+        if (need < 16) o = and4(o, byte_range(0, need));
+    }
+    store(o);
+}
+
+template <int kUnroll = kFusedUnroll>
+__device__ __forceinline__ void fused_item(const uint8_t* __restrict__ wire, uint8_t* __restrict__ out,
+                                           uint64_t total, uint64_t run, uint64_t src, uint32_t len,
+                                           uint32_t nb, uint32_t key, uint32_t lane)
+{
+    // wave-wide largest slot
+    uint32_t m = nb;
+#pragma unroll
+    for (uint32_t o = 32; o >= 1; o >>= 1) {
+        const uint32_t y = (uint32_t)__shfl_xor((int)m, o, 64);
+        m = y > m ? y : m;
+    }
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    if (m == 0) return;
+    if (m <= 1024) {
+        // G lanes per frame (G x 16 >= m), P = 64 / G frames per round
+        uint32_t G = 1;
+        while (G * 16 < m) G <<= 1;
+        const uint32_t P = 64 / G, g = lane / G, c = lane % G;
+        for (uint32_t r0 = 0; r0 < G; r0 += kUnroll) {
+            uint4 A[kUnroll], E[kUnroll];
+            FusedChunk q[kUnroll];
+            bool nl[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const uint32_t r = r0 + u;
+                const int fl = (int)((r < G ? r : 0) * P + g);
+                const uint64_t runj = __shfl(run, fl, 64), srcj = __shfl(src, fl, 64);
+                const uint32_t lenj = (uint32_t)__shfl((int)len, fl, 64);
+                const uint32_t nbj = r < G ? (uint32_t)__shfl((int)nb, fl, 64) : 0u;
+                q[u].key = (uint32_t)__shfl((int)key, fl, 64);
+                q[u].D = runj + 16 * c;
+                q[u].s = srcj + 16 * c;
+                q[u].nbytes = 16 * c < nbj ? (uint32_t)(nbj - 16 * c < 16 ? nbj - 16 * c : 16) : 0u;
+                q[u].need = q[u].nbytes && 16 * c < lenj ? (uint32_t)(lenj - 16 * c < 16 ? lenj - 16 * c : 16) : 0u;
+                nl[u] = c + 1 < G && 16 * (c + 1) < lenj;          // the next lane loads the next block
+                const uint32_t ph = (uint32_t)(q[u].s & 15u);
+                A[u] = q[u].need ? ld16(wire + (q[u].s & ~uint64_t(15))) : z;
+                E[u] = q[u].need && ph && !nl[u] && ph + q[u].need > 16
+                           ? ld16(wire + (q[u].s & ~uint64_t(15)) + 16) : z;
+            }
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const uint4 nb4 = from_next_lane(A[u], E[u]);      // every lane: DPP needs the full wave
+                if (!q[u].nbytes) continue;
+                const uint32_t ph = (uint32_t)(q[u].s & 15u);
+                uint4 o = z;
+                if (q[u].need) {
+                    o = ph ? funnel16(A[u], nl[u] ? nb4 : E[u], ph) : A[u];
+                    xor4(o, q[u].key);
+                    if (q[u].need < 16) o = and4(o, byte_range(0, q[u].need));
+                }
+                fused_store(out, q[u].D, total, o);
+            }
+        }
+        return;
+    }
+    // items with a slot over 1 KiB: frame by frame, wave-uniform
+    for (int j = 0; j < 64; ++j) {
+        const uint64_t nbj = (uint32_t)__builtin_amdgcn_readlane((int)nb, j);
+        if (nbj == 0) continue;
+        const uint64_t runj = __shfl(run, j, 64), srcj = __shfl(src, j, 64);
+        const uint64_t lenj = (uint32_t)__builtin_amdgcn_readlane((int)len, j);
+        const uint32_t kj = (uint32_t)__shfl((int)key, j, 64);
+        const uint32_t ph = (uint32_t)(srcj & 15u);
+        for (uint64_t c0 = 0; c0 < nbj; c0 += 64 * 16 * kUnroll) {
+            uint4 A[kUnroll], E[kUnroll];
+            uint32_t need[kUnroll];
+            bool nl[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u)
+                frame_chunk_load(wire, srcj, lenj, c0 + (uint64_t)u * 1024 + 16 * lane, ph, lane, A[u], E[u], need[u],
+                                 nl[u]);
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const uint64_t k0 = c0 + (uint64_t)u * 1024 + 16 * lane;
+                frame_chunk_value(A[u], E[u], need[u], nl[u], ph, kj, k0 < nbj,
+                                  [&](uint4 o) { fused_store(out, runj + k0, total, o); });
+            }
+        }
+    }
 }
 
 // Exclusive block scan of one value per thread; *block_total gets the sum.

@@ -223,3 +223,26 @@ def test_deserialize_slots_pass_kernel_routes():
     assert f(1000, 1000 * 4104, 65536).decode() == "deserialize_slots_piece_kernel"
     assert f(1000, 1000 * 1508, 16384).decode() == "deserialize_slots_piece_kernel"   # one wave per frame
     assert f(1000, 1000 * 1032, 16384).decode() == "deserialize_slots_kernel"
+
+
+# (slot, average wire bytes per frame, kernel) at n = 1000: every threshold of
+# the route from both sides
+SLOT_ROUTE_POINTS = [
+    (256, 264, "window"), (256, 136, "window"), (256, 120, "per-frame"),
+    (1024, 1032, "window"), (1024, 520, "per-frame"),
+    (2048, 2056, "piece"), (2560, 2568, "window"),
+    (4096, 4104, "piece"), (4096, 2000, "window"), (4096, 264, "per-frame"),
+    (5120, 5128, "window"), (8160, 8168, "window"), (8176, 8184, "piece"),
+    (65536, 65550, "piece"), (65536, 1041, "piece"), (65536, 1040, "per-frame"), (65536, 264, "per-frame"),
+]
+SLOT_ROUTE_KERNELS = {"window": "deserialize_slots_window_kernel", "piece": "deserialize_slots_piece_kernel",
+                      "per-frame": "deserialize_slots_kernel"}
+
+
+@pytest.mark.parametrize("slot,avg,kernel", SLOT_ROUTE_POINTS)
+def test_deserialize_slots_route_pinned(slot, avg, kernel):
+    """The slot receives' route (slots_route: window, piece or per-frame
+    kernel) at its thresholds, by slot size and the batch's average frame."""
+    from coldforce_amd import cfws
+    f = cfws.lib().cfws_deserialize_slots_pass_kernel
+    assert f(1000, 1000 * avg, slot).decode() == SLOT_ROUTE_KERNELS[kernel]

@@ -158,7 +158,8 @@ def _wire_of(payload, desc):
     return wire, starts
 
 
-@pytest.mark.parametrize("slot", [16, 48, 80, 256, 512, 992, 1008, 1504, 2016, 2032, 3008, 4064, 4080, 6000, 8160, 8176])
+@pytest.mark.parametrize("slot", [16, 48, 80, 256, 496, 512, 640, 656, 992, 1008, 1504, 2016, 2032, 3008, 4064, 4080, 6000,
+                                  8160, 8176])
 @pytest.mark.parametrize("seed", [21, 22])
 def test_slots_mixed(guards, seed, slot):
     """6,000 frames of 30-80 B (masked and not, data and control) with a

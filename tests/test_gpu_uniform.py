@@ -165,7 +165,7 @@ def _recv(wire, wire_size, n, stride, slot, cap=None, max_payload=O.DEFAULT_MAX_
     return e_st, int(odd.sum())
 
 
-@pytest.mark.parametrize("fs", [0, 1, 15, 16, 100, 125, 126, 240, 256, 512, 1000, 1024, 4064, 4096, 8160, 8161,
+@pytest.mark.parametrize("fs", [0, 1, 15, 16, 100, 125, 126, 240, 256, 482, 512, 626, 1000, 1024, 4064, 4096, 8160, 8161,
                                 65535, 65536, 200_003])
 @pytest.mark.parametrize("mask", [1, 0])
 def test_uniform_receive_sizes(fs, mask):
