@@ -624,24 +624,20 @@ h2_msg_apply_units_kernel(cfws_frame_desc_t* __restrict__ mdesc, int32_t* __rest
     cfws_frame_desc_t M = {};
     int32_t ms = CFWS_PARSE_MORE_DATA;
     if (m < n) {
-        // deserialize_plan_apply_kernel's row m
+        // the receive layout's row m (cfws_kernels.h), without reassembly
         vals[m] = run;
         M = mdesc[m];
         M.payload_off = run;
         mdesc[m].payload_off = run;
         ms = mstatus[m];
-        if (ms == CFWS_PARSE_COMPLETE && M.payload_size > 0 && run + M.payload_size > capacity) {
+        if (de_capacity_rule(ms, M.payload_size, run, capacity) != ms) {
             ms = CFWS_ERROR_OUT_OF_MEMORY;
             mstatus[m] = ms;
         }
         map_range(run, run + v, m, t, mmap);
         if (m == n - 1) {
             mmap[(t + kRegion - 1) / kRegion] = (uint32_t)m;
-            hdr[0] = t;
-            hdr[1] = 0;
-            hdr[2] = t;
-            if (self_scan) hdr[3] = g;
-            if (user_total) *user_total = t;
+            de_epilogue(hdr, user_total, t, g, self_scan);
         }
     }
     if (m == 0) *pass_total = *pooled_p <= pool_cap ? t : 0;

@@ -1,11 +1,12 @@
 // cfws_kernels.h -- device code and launch helpers shared by the codec's
-// translation units (cfws_device.hip: WS plan / execute / batch ABI and the
-// small-batch path; cfws_slots.hip: the receive into fixed slots;
-// cfws_h2.hip: WebSocket over HTTP/2; cfws_ops.hip: split ops, handshake
-// keys, device indexing, copies and fills). Everything here is
-// internal to each unit (anonymous namespace); the error state and the
-// deserialize plan, which the units share, are defined once in
-// cfws_device.hip (namespace cfws_rt).
+// translation units (cfws_device.hip: WS execute / batch ABI and the
+// small-batch path; cfws_plan.hip: the WS plans and the fused deserialize;
+// cfws_slots.hip: the receive into fixed slots; cfws_h2.hip: WebSocket over
+// HTTP/2; cfws_ops.hip: split ops, handshake keys, device indexing, copies
+// and fills). Everything here is internal to each unit (anonymous
+// namespace); what the units share is defined once (namespace cfws_rt): the
+// error state in cfws_device.hip, the deserialize plan and the fused
+// deserialize in cfws_plan.hip.
 #ifndef CFWS_KERNELS_H
 #define CFWS_KERNELS_H
 
@@ -35,6 +36,10 @@ int deserialize_plan_impl(const void* d_wire, uint64_t wire_size, const uint64_t
                           const uint64_t* d_ends, size_t n, uint64_t max_payload, uint32_t align,
                           uint32_t flags, cfws_frame_desc_t* d_desc, int32_t* d_status, uint64_t cap,
                           uint64_t* d_total, void* ws, size_t ws_size, void* stream);
+// cfws_deserialize_batch's fused plan + copy; the caller has checked the arguments
+int deserialize_fused_impl(const void* d_wire, uint64_t wire_size, const uint64_t* d_index, size_t n,
+                           uint64_t max_payload, uint32_t align, cfws_frame_desc_t* d_desc, int32_t* d_status,
+                           void* d_payload, uint64_t cap, uint64_t* d_total, void* ws, void* stream);
 }  // namespace cfws_rt
 
 namespace {
@@ -1503,7 +1508,7 @@ __device__ __forceinline__ uint4 ld16u(const uint8_t* p)
 }
 
 // ---- a wave copies the frames its lanes parsed --------------------------------
-// The copy of the fused deserialize (cfws_device.hip) and of the slot
+// The copy of the fused deserialize (cfws_plan.hip) and of the slot
 // receive (cfws_slots.hip). Per item (lane l: one frame), the wave's largest
 // slot sets how many frames share one wave-instruction: groups of G lanes
 // (G x 16 bytes >= the slot), one frame per group; items with a slot over
@@ -1816,78 +1821,6 @@ __device__ __forceinline__ void prefix_from_partials(const uint64_t* __restrict_
     block_exclusive_scan(xa, s_wave, &all);
 }
 
-// ---- single-pass plans (more than kSelfScanBlocks blocks) --------------------
-// A plan of many blocks scans its block sums with a decoupled look-back
-// instead of a scan launch and a second pass over the frames: each block
-// takes a ticket (so every lower ticket is already running), publishes its
-// sum (flag 1), finds its exclusive prefix from the words of the blocks
-// below it, 64 at a time, and publishes the inclusive prefix (flag 2). A
-// block's flag and value are one 64-bit word (value << 2 | flag: sums below
-// 2^62 bytes, far above any arena), stored and
-// loaded whole by device-scope atomics (coherent across the XCDs' L2s by
-// themselves), so a reader never sees a flag without its value and nothing
-// has to be ordered: a publish is one store the block does not wait for, a
-// poll one load. (The first form kept flags and values apart: each publish
-// waited for its value's store before the flag's, and each poll loaded the
-// value after the flag -- two more round trips per block, which under a
-// saturated memory system bound the plans by look-back latency. Release /
-// acquire fences would write back and invalidate the whole L2 at each
-// publish and each poll: measured 2 ms per plan on 16 K blocks.)
-//
-// The words live in the workspace's look area after the u32 ticket (word
-// 0), the u32 flag words 1..sb + 1 that some plans leave for their execute,
-// and padding to 8 bytes (look_state_index, look_bytes); all of it is zeroed
-// before the launch.
-
-__device__ __forceinline__ uint64_t* look_states(uint32_t* look)
-{
-    return reinterpret_cast<uint64_t*>(look + look_state_index(gridDim.x));
-}
-
-__device__ __forceinline__ uint32_t plan_ticket(uint32_t* look, uint32_t* s_bid)
-{
-    if (threadIdx.x == 0) *s_bid = __hip_atomic_fetch_add(look, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    return *s_bid;
-}
-
-// Wave 0 of block b (every lane): b's exclusive prefix, after publishing
-// `total` as b's sum; then b's inclusive prefix is published. Blocks below
-// b that have not published yet (flag 0) hold a lower ticket, so they are
-// running and publish without waiting on anyone.
-__device__ __forceinline__ uint64_t plan_lookback(uint32_t b, uint64_t total, uint64_t* state)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    if (b == 0) {
-        if (lane == 0) __hip_atomic_store(&state[0], total << 2 | 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return 0;
-    }
-    if (lane == 0) __hip_atomic_store(&state[b], total << 2 | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint64_t excl = 0;
-    int64_t hi = (int64_t)b - 1;                      // window [hi - 63, hi], lane l: hi - l
-    while (true) {
-        const int64_t i = hi - (int64_t)lane;
-        uint64_t w = 2u;                              // below block 0: an inclusive 0
-        if (i >= 0) {
-            do {
-                w = __hip_atomic_load(&state[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((w & 3u) == 0u) __builtin_amdgcn_s_sleep(2);
-            } while ((w & 3u) == 0u);
-        }
-        // the nearest inclusive prefix (lowest lane) ends the walk
-        const uint64_t pm = __ballot((w & 3u) == 2u);
-        const uint32_t stop = pm ? (uint32_t)__builtin_ctzll(pm) : 64u;
-        uint64_t c = lane <= stop ? w >> 2 : 0;
-#pragma unroll
-        for (uint32_t o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-        excl += c;
-        if (pm) break;
-        hi -= 64;
-    }
-    if (lane == 0) __hip_atomic_store(&state[b], (excl + total) << 2 | 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return excl;
-}
-
 // ---- plans: two launches each (three above kSelfScanBlocks blocks) ---------
 // 1. per frame: sizes (serialize: header size, co_ws_frame.c:41-91;
 //    deserialize: the header decode) + the block's sum;
@@ -1896,9 +1829,54 @@ __device__ __forceinline__ uint64_t plan_lookback(uint32_t b, uint64_t total, ui
 // 3. per block: exclusive offsets of its frames, then everything the
 //    offsets decide (descriptor offsets, capacity rule, region maps, totals).
 
-// Offsets into the descriptors, the capacity rule (a COMPLETE frame with a
-// payload that does not fit gets CFWS_ERROR_OUT_OF_MEMORY, like the
-// reference's failed malloc, co_ws_frame.c:216-223), region maps, totals.
+// The layout rows, on plain values, for every form of a plan (two-launch,
+// single-pass, fused, small-batch, the HTTP/2 message layout).
+// Receive: a slot is the payload of a COMPLETE frame, rounded up to `align`
+// (a power of two; 1: packed).
+__device__ __forceinline__ uint64_t de_slot_bytes(int32_t st, uint64_t payload_size, uint64_t align)
+{
+    const uint64_t len = (st == CFWS_PARSE_COMPLETE) ? payload_size : 0;
+    return (len + align - 1) & ~(align - 1);
+}
+
+// Receive, the capacity rule: a COMPLETE frame with a payload that does not
+// fit at `off` gets CFWS_ERROR_OUT_OF_MEMORY, like the reference's failed
+// malloc (co_ws_frame.c:216-223).
+__device__ __forceinline__ int32_t de_capacity_rule(int32_t st, uint64_t payload_size, uint64_t off,
+                                                    uint64_t capacity)
+{
+    const bool oom = st == CFWS_PARSE_COMPLETE && payload_size > 0 && off + payload_size > capacity;
+    return oom ? CFWS_ERROR_OUT_OF_MEMORY : st;
+}
+
+// The last frame's epilogue of a one-pass layout, t = min(g, capacity);
+// own_g: no scan launch has stored the grand total g. The receive reports
+// the CLAMPED total to the caller, the send the UNCLAMPED one (the wire size
+// the batch needs).
+__device__ __forceinline__ void de_epilogue(uint64_t* hdr, uint64_t* user_total, uint64_t t, uint64_t g,
+                                            bool own_g = true)
+{
+    hdr[0] = t;
+    hdr[1] = 0;
+    hdr[2] = t;
+    if (own_g) hdr[3] = g;
+    if (user_total) *user_total = t;
+}
+
+__device__ __forceinline__ void ser_epilogue(uint64_t* hdr, uint64_t* user_total, uint64_t t, uint64_t g,
+                                             bool own_g = true)
+{
+    hdr[0] = t;
+    if (own_g) hdr[3] = g;
+    if (user_total) *user_total = g;
+}
+
+// Send: a frame's wire bytes from hs = header_size_of(len, mask), which the
+// callers keep for the descriptor (deriving it again in here cost
+// serialize_plan_reduce_kernel two VGPRs).
+__device__ __forceinline__ uint64_t ser_wire_bytes(uint32_t hs, uint64_t len) { return hs + len; }
+
+// Offsets into the descriptors, the capacity rule, region maps, totals.
 __global__ void __launch_bounds__(kThreads)
 deserialize_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, int32_t* __restrict__ status,
                               uint64_t* __restrict__ vals0, uint64_t* __restrict__ vals1, uint64_t n,
@@ -1946,8 +1924,8 @@ deserialize_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, int32_t* __r
             const bool ctl = reassemble && is_control(desc[f].opcode);
             const uint64_t off = ctl ? g0 + run1 : run0;
             desc[f].payload_off = off;
-            const uint64_t len = desc[f].payload_size;
-            if (status[f] == CFWS_PARSE_COMPLETE && len > 0 && off + len > capacity)
+            const int32_t st = status[f];
+            if (de_capacity_rule(st, desc[f].payload_size, off, capacity) != st)
                 status[f] = CFWS_ERROR_OUT_OF_MEMORY;
             map_range(run0, run0 + v0[k], f, t0, map0);
             if (reassemble) {
@@ -2028,6 +2006,62 @@ inline int zero_totals(const WsLayout& L, void* ws, uint64_t* d_total, hipStream
     (void)hipMemsetAsync(ws_ptr<uint64_t>(ws, L.hdr), 0, 64, st);
     if (d_total) (void)hipMemsetAsync(d_total, 0, 8, st);
     return launch_check("zero totals");
+}
+
+// The flag word the serialize plan leaves for the execute: 0 = in-region
+// edges (the single-pass plan found every frame qualifying), else not. It
+// sits after the single-pass plan's ticket and block flags, inside the
+// look area (>= 64 words, and >= n / 256 + 1); hence that plan's frames per
+// thread and threads per block here (cfws_plan.hip has the measurements).
+#ifndef CFWS_SINGLE_ITEMS_SER
+#define CFWS_SINGLE_ITEMS_SER 8
+#endif
+#ifndef CFWS_SER_PLAN_THREADS
+#define CFWS_SER_PLAN_THREADS 512
+#endif
+constexpr int kSingleItemsSer = CFWS_SINGLE_ITEMS_SER;
+constexpr int kSerPlanThreads = CFWS_SER_PLAN_THREADS;
+inline uint32_t* ser_inreg_flag(const WsLayout& L, const void* ws, uint64_t n)
+{
+    return ws_ptr<uint32_t>(ws, L.look) + grid_for(n, uint64_t(kSerPlanThreads) * kSingleItemsSer) + 1;
+}
+
+// The argument checks of the WS plan and execute stages: the first failing
+// check's code and message (code CFWS_OK: accepted), no side effect. A
+// stage's entry point reports it through set_err; the batch entry points ask
+// both stages before they take a single-launch form.
+struct ArgCheck { int code; const char* what; };
+constexpr ArgCheck kArgsOk = {CFWS_OK, ""};
+
+inline ArgCheck check_ser_plan(const void* d_desc, size_t n, uint64_t cap, const void* ws, size_t ws_size)
+{
+    if (!ws || ws_size < ws_layout(n, cap).bytes) return {CFWS_ERROR_WORKSPACE, "workspace too small"};
+    if (n > 0xffffffffull) return {CFWS_ERROR_INVALID_ARGUMENT, "too many frames"};
+    if (n != 0 && !d_desc) return {CFWS_ERROR_INVALID_ARGUMENT, "null descriptor table"};
+    return kArgsOk;
+}
+
+inline ArgCheck check_de_plan(const void* d_wire, const void* d_index, size_t n, uint32_t align, uint32_t flags,
+                              const void* d_desc, const void* d_status, uint64_t cap, const void* ws,
+                              size_t ws_size)
+{
+    if (align == 0 || (align & (align - 1)) || align > 4096)
+        return {CFWS_ERROR_INVALID_ARGUMENT, "align must be a power of two <= 4096"};
+    if (flags & ~CFWS_DESERIALIZE_REASSEMBLE) return {CFWS_ERROR_INVALID_ARGUMENT, "unknown flags"};
+    if (!ws || ws_size < ws_layout(n, cap).bytes) return {CFWS_ERROR_WORKSPACE, "workspace too small"};
+    if (n > 0xffffffffull) return {CFWS_ERROR_INVALID_ARGUMENT, "too many frames"};
+    if (n != 0 && (!d_wire || !d_index || !d_desc || !d_status)) return {CFWS_ERROR_INVALID_ARGUMENT, "null pointer"};
+    return kArgsOk;
+}
+
+// Either execute: the arenas, then its other pointers (an empty call needs none).
+template <typename... P>
+ArgCheck check_execute(size_t n, uint64_t cap, const void* d_payload, const void* d_wire, P... others)
+{
+    if (n == 0 || cap == 0) return kArgsOk;
+    if (!d_payload || !d_wire || (... || !others)) return {CFWS_ERROR_INVALID_ARGUMENT, "null pointer"};
+    if (misaligned(d_payload, d_wire)) return {CFWS_ERROR_INVALID_ARGUMENT, "arenas must be 16-byte aligned"};
+    return kArgsOk;
 }
 
 // Dynamic LDS the streaming kernel reserves per workgroup. It is never
