@@ -597,6 +597,8 @@ int slots_impl(const SlotsArgs& a, bool scatter, void* stream, const char* what)
         return set_err(CFWS_ERROR_INVALID_ARGUMENT, "null pointer", hipSuccess);
     if (misaligned(a.out, a.wire))
         return set_err(CFWS_ERROR_INVALID_ARGUMENT, "arenas must be 16-byte aligned", hipSuccess);
+    if (reinterpret_cast<uintptr_t>(a.info) & 7u)          // slot_info stores each entry as one uint2
+        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "info entries must be 8-byte aligned", hipSuccess);
     const CfwsPassTimer timer(st);
     const SlotsRoute route = slots_route(a.slot, a.n, a.wire_size);
     if (route == kSlotsWindow) {

@@ -111,7 +111,7 @@ int cfws_serialize_batch(const void* d_payload, cfws_frame_desc_t* d_desc,
  * header size (2..14, co_ws_frame.c:34-91) + payload_size. One launch, no
  * workspace; the bytes are those cfws_serialize_batch writes for the same
  * frames. Wire bytes at or past wire_capacity are not written;
- * *d_wire_total (may be NULL) = n * W. payload_size <= 2^31, n * W < 2^40. */
+ * *d_wire_total (may be NULL) = n * W. payload_size <= 2^30, n * W < 2^40. */
 int cfws_serialize_uniform(const void* d_payload, const uint32_t* d_keys, size_t n_frames,
                            uint64_t payload_size, uint8_t fin, uint8_t opcode, uint8_t mask,
                            void* d_wire, uint64_t wire_capacity, uint64_t* d_wire_total,
@@ -192,8 +192,9 @@ typedef struct cfws_frame_info {
 } cfws_frame_info_t;
 
 /* cfws_deserialize_slots / cfws_deserialize_scatter with d_info[i] (8-byte
- * aligned) in place of d_desc[i] and d_status[i]: the same decisions, the
- * same payload bytes; the fields equal the descriptor form's. */
+ * aligned; CFWS_ERROR_INVALID_ARGUMENT otherwise) in place of d_desc[i] and
+ * d_status[i]: the same decisions, the same payload bytes; the fields equal
+ * the descriptor form's. */
 int cfws_deserialize_slots_info(const void* d_wire, uint64_t wire_size,
                                 const uint64_t* d_frame_index, size_t n_frames,
                                 uint64_t max_payload, uint64_t slot_bytes,

@@ -21,6 +21,14 @@ tests/test_knobs.py runs this script once per setting):
   CFWS_SLOT_GRID=N      the fixed-slot window kernel as a grid-stride loop
                         over N workgroups
 
+With the argument `uniform`, only the uniform send (cfws_serialize_uniform)
+over tests/test_uniform_cover.py's knob sweep, for its two knobs:
+
+  CFWS_UNIFORM_SPAN2_MIN=N  the small kernel on 2 KiB spans from N-byte
+                        payloads (0: every payload; 2^30: none, 4 KiB spans)
+  CFWS_UNIFORM_LDS=N    LDS reserved per workgroup by the uniform send's
+                        small and general kernels (0: none)
+
 Each case is checked byte for byte against the oracle. Prints "KNOB OK".
 """
 import os
@@ -88,8 +96,34 @@ def h2_send(sizes, rng, S=16384):
     assert np.array_equal(h2[:len(exp)].cpu().numpy(), exp), "h2 send != oracle"
 
 
+def uniform_send():
+    """The uniform send on the span CFWS_UNIFORM_SPAN2_MIN selects (n: one
+    period of that span, test_uniform_cover.py), whole and with one capacity
+    cut, against the oracle and cfws_serialize_batch (test_gpu_uniform._run)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_uniform as TU
+    import test_uniform_cover as cover
+    min2 = int(os.environ.get("CFWS_UNIFORM_SPAN2_MIN", "1024"))
+    for fs in cover.KNOB_PAYLOADS:
+        for mask in (1, 0):
+            span = cover.default_span(fs, mask, span2_min=min2)
+            assert (fs, mask, span) in cover.COVERED
+            n = cover.period_frames(fs, mask, span)
+            TU._run(n, fs, mask, seed=fs + mask)
+            TU._run(n, fs, mask, seed=fs + mask, cap=n * cover.frame_bytes(fs, mask) // 2 + 3)
+    fs, n = cover.KNOB_GENERAL
+    for mask in (1, 0):
+        TU._run(n, fs, mask, seed=fs + mask)
+        TU._run(n, fs, mask, seed=fs + mask, cap=n * cover.frame_bytes(fs, mask) // 2 + 3)
+
+
 def main():
     cfws.init()
+    if sys.argv[1:] == ["uniform"]:
+        uniform_send()
+        print("KNOB OK", {k: v for k, v in os.environ.items() if k.startswith("CFWS_")}, flush=True)
+        return
+    assert not sys.argv[1:], f"unknown section {sys.argv[1:]}"
     rng = np.random.default_rng(11)
     # mixed sizes: fast / two-frame / general regions, edges, 64-bit lengths
     sizes = rng.choice([0, 1, 3, 125, 126, 1000, 4096, 65535, 65536, 70000], size=3000)

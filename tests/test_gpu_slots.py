@@ -249,6 +249,14 @@ def test_slots_arguments(guards):
                                                                                 device="cuda"))
     torch.cuda.synchronize()
     assert tot.item() == 0
+    # d_info must be 8-byte aligned (an entry is stored as one 8-byte word):
+    # 4 bytes off is refused and nothing is written
+    inf = guards(16)
+    rc = cfws.lib().cfws_deserialize_slots_info(w.data_ptr(), 64, idx.data_ptr(), 1, 1 << 20, 16, inf.data_ptr() + 4,
+                                                out.data_ptr(), 64, None, cfws._stream(None))
+    torch.cuda.synchronize()
+    assert rc == cfws.ERROR_INVALID_ARGUMENT
+    assert (inf.download() == SENT).all() and (out.download() == SENT).all()
 
 
 @pytest.mark.parametrize("slot", [16, 256, 2048, 16384])

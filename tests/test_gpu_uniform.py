@@ -18,6 +18,7 @@ torch = pytest.importorskip("torch")
 
 from coldforce_amd import cfws  # noqa: E402
 from coldforce_amd import workloads as W  # noqa: E402
+import test_uniform_cover as cover  # noqa: E402  (the shapes, and the proof that they suffice)
 
 SENT = 0xEE
 
@@ -82,23 +83,83 @@ def test_uniform_sizes(fs, mask):
 @pytest.mark.parametrize("fin,opcode", [(1, 1), (0, 0), (1, 9), (1, 0x7F), (0, 0xFF)])
 def test_uniform_header_bytes(fin, opcode):
     """b0 = opcode verbatim | 0x80 when fin (co_ws_frame.c:34-39)."""
-    for fs in (7, 300, 70000):
+    for fs in (7, 300, 70000, 48, 1024):                # bytes, general, general, small <4>, small <2>
         _run(64, fs, 1, fin, opcode, seed=fs)
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 63, 64, 65, 1023, 4097])
+@pytest.mark.parametrize("n", [1, 2, 3, 63, 64, 65, 1023, 4097, 127, 128, 129, 2049])
 def test_uniform_counts(n):
-    for fs in (3, 250, 2000):
+    """32 and 256: the small kernel on 4 KiB spans, whose key window is 128
+    frames (clipped to the batch's last n - F0) and whose last span ends
+    past the batch."""
+    for fs in (3, 250, 2000, 32, 256):
         _run(n, fs, 1, seed=n)
 
 
 def test_uniform_capacity_cuts():
     """Wire bytes at or past the capacity are never written, at cuts inside
-    headers, payloads and chunks."""
-    for fs in (5, 256, 1000):
+    headers, payloads and chunks, and around the end of a wave's first and
+    second span (32 .. 256: 4 KiB spans; 1024, 2000: 2 KiB; 57: the general
+    kernel with a second header round)."""
+    for fs in (5, 256, 1000, 32, 112, 1024, 2000, 57):
         total = 777 * cfws.uniform_frame_bytes(fs, True)
-        for cap in (0, 1, 7, 16, 17, 33, total // 2 + 3, total - 17, total - 1, total):
+        span = cover.default_span(fs, 1)
+        for cap in (0, 1, 7, 16, 17, 33, total // 2 + 3, total - 17, total - 1, total,
+                    span - 17, span - 1, span, span + 1, span + 16, 2 * span - 1):
             _run(777, fs, 1, cap=cap, seed=cap % 97)
+
+
+def _kernel(fs, mask):
+    return cfws.lib().cfws_serialize_uniform_pass_kernel(fs, mask).decode()
+
+
+@pytest.mark.parametrize("fs,mask", cover.SMALL_CASES)
+def test_uniform_small_kernel_period(fs, mask):
+    """serialize_uniform_small_kernel over one period of (frame, span) phase
+    (test_uniform_cover.py: every kind of chunk at every header position,
+    also as the last chunk of a span): 7-bit lengths (payloads up to 112,
+    headers of 2 / 6 bytes, which a chunk may cut), up to 110 frames' keys
+    per span, and the largest payload the kernel takes."""
+    assert _kernel(fs, mask) == "serialize_uniform_small_kernel"
+    _run(cover.period_frames(fs, mask), fs, mask, seed=fs + mask)
+
+
+@pytest.mark.parametrize("fs,mask", cover.GENERAL_SHORT + cover.BYTES_NEIGHBOURS)
+def test_uniform_general_short_frames(fs, mask):
+    """serialize_uniform_kernel at 32 .. 67 wire bytes a frame: up to 63,
+    more than 32 headers meet a 2 KiB span and the header pass takes a second
+    round (test_uniform_cover.py). W = 31 on the other side of the boundary
+    takes the bytes kernel."""
+    general = (fs, mask) in cover.GENERAL_SHORT
+    assert _kernel(fs, mask) == ("serialize_uniform_kernel" if general else "serialize_uniform_bytes_kernel")
+    _run(cover.period_frames(fs, mask), fs, mask, seed=fs + mask)
+
+
+def test_uniform_payload_limit():
+    """payload_size <= 2^30 (include/cfws.h; the kernels' 32-bit source
+    offsets rely on it): one byte more is refused, 2^30 itself is sent. The
+    payload is zeros, so the wire is the 14-byte header and then the key
+    repeating; the first 4,096 bytes are compared, the rest is past the
+    capacity."""
+    fs, cap = 1 << 30, 4096
+    pay = torch.zeros(fs + 16, dtype=torch.uint8, device="cuda")
+    wire = torch.full((cap + 4096,), SENT, dtype=torch.uint8, device="cuda")
+    keys = O.keys(30, 1)
+    keys_t = torch.from_numpy(keys.view(np.int32)).cuda()
+    with pytest.raises(cfws.CodecError):
+        cfws.serialize_uniform(pay, keys_t, 1, fs + 1, wire, mask=True, wire_capacity=cap)
+    torch.cuda.synchronize()
+    assert (wire == SENT).all()
+    tot = torch.zeros(1, dtype=torch.int64, device="cuda")
+    cfws.serialize_uniform(pay, keys_t, 1, fs, wire, fin=True, opcode=2, mask=True, total_t=tot, wire_capacity=cap)
+    torch.cuda.synchronize()
+    assert int(tot.item()) == fs + 14
+    k = np.frombuffer(keys.astype("<u4").tobytes(), np.uint8)
+    exp = np.concatenate([np.frombuffer(bytes([0x82, 0xFF]) + fs.to_bytes(8, "big"), np.uint8), k,
+                          np.tile(k, cap // 4)])[:cap]
+    got = wire.cpu().numpy()
+    assert np.array_equal(got[:cap], exp)
+    assert (got[cap:] == SENT).all()
 
 
 def test_uniform_empty_and_arguments():
@@ -112,6 +173,8 @@ def test_uniform_empty_and_arguments():
         cfws.serialize_uniform(pay, None, 2, 10, wire, mask=True)
     with pytest.raises(cfws.CodecError):                   # payload over 2^31
         cfws.serialize_uniform(pay, None, 1, (1 << 31) + 1, wire, mask=False)
+    with pytest.raises(cfws.CodecError):                   # ... and over 2^30, the limit
+        cfws.serialize_uniform(pay, None, 1, (1 << 30) + 1, wire, mask=False)
     with pytest.raises(cfws.CodecError):                   # misaligned wire
         cfws.serialize_uniform(pay, None, 2, 10, wire[1:], mask=False)
 
@@ -231,6 +294,14 @@ def test_uniform_receive_arguments():
     rc = cfws.lib().cfws_deserialize_slots_uniform(cfws._p(w), 64, 4, 20, 1 << 20, 16, None, cfws._p(out), 64,
                                                    None, None, cfws._stream(None))
     assert rc == cfws.ERROR_INVALID_ARGUMENT                # no info entries
+    # info entries are stored as one 8-byte word each: 4 bytes off is refused, nothing written
+    info9 = torch.full((9, 4), SENT, dtype=torch.uint8, device="cuda")
+    out_s = torch.full((64,), SENT, dtype=torch.uint8, device="cuda")
+    rc = cfws.lib().cfws_deserialize_slots_uniform(cfws._p(w), 64, 4, 16, 1 << 20, 16, info9.data_ptr() + 4,
+                                                   cfws._p(out_s), 64, None, None, cfws._stream(None))
+    torch.cuda.synchronize()
+    assert rc == cfws.ERROR_INVALID_ARGUMENT
+    assert (info9 == SENT).all() and (out_s == SENT).all()
     mm = torch.full((1,), 7, dtype=torch.int32, device="cuda")
     tot = torch.full((1,), 7, dtype=torch.int64, device="cuda")
     cfws.deserialize_slots_uniform(w, 64, 0, 20, out, 16, info, total_t=tot, mismatch_t=mm)

@@ -32,3 +32,24 @@ def test_parity_under_knob(knobs):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "knob_parity.py")], env=env,
                        capture_output=True, text=True, timeout=240)
     assert r.returncode == 0 and "KNOB OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+# cfws_serialize_uniform's two knobs, over the uniform section alone: every
+# small-kernel payload on 2 KiB spans (a 7-bit-length header there only under
+# the knob), every one on 4 KiB spans (a 64 KiB payload there likewise), and
+# the LDS reservation set and cleared for both kernels that take it
+UNIFORM_KNOBS = [
+    {"CFWS_UNIFORM_SPAN2_MIN": "0"},
+    {"CFWS_UNIFORM_SPAN2_MIN": "1073741824"},
+    {"CFWS_UNIFORM_LDS": "32000"},
+    {"CFWS_UNIFORM_LDS": "0"},
+]
+
+
+@pytest.mark.parametrize("knobs", UNIFORM_KNOBS, ids=lambda k: ",".join(f"{a[5:]}={b}" for a, b in k.items()))
+def test_uniform_send_under_knob(knobs):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CFWS_")}
+    env.update(knobs)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "knob_parity.py"), "uniform"], env=env,
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0 and "KNOB OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
