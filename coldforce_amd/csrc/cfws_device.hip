@@ -1,10 +1,11 @@
 // cfws_device.hip -- MI355X (gfx950) WebSocket frame codec: the batch C ABI
 // (include/cfws.h: serialize / deserialize execute and batch, and the route
 // a batch takes), the single-launch small-batch kernels, and the library's
-// error state and device probe. The plans and the fused deserialize are in
-// cfws_plan.hip; the streaming kernel and the device code the units share
-// in cfws_kernels.h; the receive into fixed slots in cfws_slots.hip; HTTP/2
-// in cfws_h2.hip; the smaller ops in cfws_ops.hip.
+// runtime: error state, device probe and pass timing. The plans and the
+// fused deserialize are in cfws_plan.hip; the streaming kernel and the
+// device code the units share in cfws_kernels.h; the receive into fixed
+// slots in cfws_slots.hip; HTTP/2 in cfws_h2.hip; the split ops in
+// cfws_split.hip; the smaller ops in cfws_ops.hip.
 //
 // Reference behaviour restated on the device:
 //   header encode        co_ws_frame.c:34-68, :70-91
@@ -98,6 +99,50 @@ int launch_check(const char* what)
 }
 
 }  // namespace cfws_rt
+
+// Pass timing (cfws_internal.h): the calling thread's pending event pair and
+// the open public call's.
+CfwsPassEvents& cfws_internal_pass_events()
+{
+    thread_local CfwsPassEvents e = {nullptr, nullptr};
+    return e;
+}
+
+namespace {
+thread_local CfwsPassEvents t_call_pass = {nullptr, nullptr};   // the open call's pair
+thread_local int t_pass_depth = 0;                               // open public calls
+}  // namespace
+
+CfwsPassScope::CfwsPassScope()
+{
+    if (t_pass_depth++ == 0) {
+        CfwsPassEvents& pe = cfws_internal_pass_events();
+        t_call_pass = pe;
+        pe = {nullptr, nullptr};
+    }
+}
+
+CfwsPassScope::~CfwsPassScope()
+{
+    if (--t_pass_depth == 0) t_call_pass = {nullptr, nullptr};
+}
+
+CfwsPassEvents cfws_internal_take_pass()
+{
+    const CfwsPassEvents e = t_call_pass;
+    t_call_pass = {nullptr, nullptr};
+    return e;
+}
+
+CfwsPassTimer::CfwsPassTimer(void* s) : e(cfws_internal_take_pass()), stream(s)
+{
+    if (e.start) (void)hipEventRecord(static_cast<hipEvent_t>(e.start), static_cast<hipStream_t>(stream));
+}
+
+CfwsPassTimer::~CfwsPassTimer()
+{
+    if (e.stop) (void)hipEventRecord(static_cast<hipEvent_t>(e.stop), static_cast<hipStream_t>(stream));
+}
 
 namespace {
 
@@ -302,7 +347,7 @@ serialize_small_kernel(const uint8_t* __restrict__ src, cfws_frame_desc_t* __res
             s_src[f] = d.payload_off;
             s_len[f] = d.payload_size;
             s_key[f] = d.mask() ? d.key() : 0u;
-            s_hb[f] = ((d.opcode() | (d.fin() ? 0x80u : 0u)) & 0xffu) | (d.mask() ? 0x100u : 0u) | hs << 16;
+            s_hb[f] = d.header_word0() | hs << 16;
         }
     }
     const uint64_t g = small_scan(w, n, s_off, s_wave);      // (its barrier publishes the views)
@@ -430,6 +475,14 @@ int cfws_init(void) { return check_init(); }
 int cfws_init_device(int device) { return cfws_rt::check_device(device); }
 const char* cfws_last_error(void) { return g_err; }
 const char* cfws_version(void) { return "cfws 0.2 gfx950"; }
+
+int cfws_time_next_pass(void* start, void* stop)
+{
+    if ((start == nullptr) != (stop == nullptr))
+        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "start and stop events go together", hipSuccess);
+    cfws_internal_pass_events() = {start, stop};
+    return CFWS_OK;
+}
 
 size_t cfws_workspace_size(size_t n_frames, uint64_t out_capacity)
 {

@@ -2,11 +2,13 @@
 // translation units (cfws_device.hip: WS execute / batch ABI and the
 // small-batch path; cfws_plan.hip: the WS plans and the fused deserialize;
 // cfws_slots.hip: the receive into fixed slots; cfws_h2.hip: WebSocket over
-// HTTP/2; cfws_ops.hip: split ops, handshake keys, device indexing, copies
-// and fills). Everything here is internal to each unit (anonymous
-// namespace); what the units share is defined once (namespace cfws_rt): the
-// error state in cfws_device.hip, the deserialize plan and the fused
-// deserialize in cfws_plan.hip.
+// HTTP/2; cfws_split.hip: the split header / payload ops; cfws_ops.hip:
+// handshake keys, device indexing, copies, fills and the drop-in service).
+// Everything here is internal to each unit (anonymous namespace); what the
+// units share is defined once (namespace cfws_rt): the error state and the
+// pass timing in cfws_device.hip; the deserialize plan, the fused
+// deserialize, the scan kernels and the two-launch deserialize apply in
+// cfws_plan.hip.
 #ifndef CFWS_KERNELS_H
 #define CFWS_KERNELS_H
 
@@ -40,13 +42,39 @@ int deserialize_plan_impl(const void* d_wire, uint64_t wire_size, const uint64_t
 int deserialize_fused_impl(const void* d_wire, uint64_t wire_size, const uint64_t* d_index, size_t n,
                            uint64_t max_payload, uint32_t align, cfws_frame_desc_t* d_desc, int32_t* d_status,
                            void* d_payload, uint64_t cap, uint64_t* d_total, void* ws, void* stream);
+
+// Kernels more than one unit launches, defined in cfws_plan.hip (a unit that
+// only declares a kernel launches the defining unit's).
+// Exclusive scan of n values in place, kScanBlock per block: per-block sums,
+// one workgroup's scan of those (*grand: the total), then each block's scan
+// from its prefix; run_scan is the three launches.
+__global__ void scan_reduce_kernel(const uint64_t* __restrict__ vals, uint64_t n, uint64_t* __restrict__ partials);
+__global__ void scan_partials_kernel(uint64_t* __restrict__ partials, uint64_t nb, uint64_t* __restrict__ grand);
+// scan_partials_kernel for up to two passes in one launch (block p: pass p)
+__global__ void scan_partials2_kernel(uint64_t* __restrict__ partials0, uint64_t* __restrict__ partials1, uint64_t nb,
+                                      uint64_t* __restrict__ grand0, uint64_t* __restrict__ grand1);
+__global__ void scan_apply_kernel(uint64_t* __restrict__ vals, uint64_t n, const uint64_t* __restrict__ partials);
+int run_scan(uint64_t* vals, uint64_t n, uint64_t* partials, uint64_t* grand, hipStream_t st);
+// The two-launch deserialize plan's second step: offsets into the
+// descriptors, the capacity rule, region maps, totals.
+__global__ void deserialize_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, int32_t* __restrict__ status,
+                                              uint64_t* __restrict__ vals0, uint64_t* __restrict__ vals1, uint64_t n,
+                                              const uint64_t* __restrict__ partials0,
+                                              const uint64_t* __restrict__ partials1, uint64_t nb,
+                                              uint32_t self_scan, uint64_t* __restrict__ hdr,
+                                              uint64_t capacity, uint32_t reassemble, uint32_t* __restrict__ map0,
+                                              uint32_t* __restrict__ map1, uint64_t* __restrict__ user_total);
 }  // namespace cfws_rt
 
 namespace {
 
 using cfws_rt::check_init;
+using cfws_rt::deserialize_plan_apply_kernel;
 using cfws_rt::deserialize_plan_impl;
 using cfws_rt::launch_check;
+using cfws_rt::run_scan;
+using cfws_rt::scan_partials2_kernel;
+using cfws_rt::scan_partials_kernel;
 using cfws_rt::set_err;
 
 constexpr int kThreads = 256;
@@ -152,6 +180,11 @@ struct DescWords {
     __device__ uint32_t opcode() const { return (uint32_t)(w3 >> 40) & 0xffu; }
     __device__ uint32_t mask() const { return (uint32_t)(w3 >> 48) & 0xffu; }
     __device__ uint32_t header_size() const { return (uint32_t)(w3 >> 56); }
+    // WS header byte 0 (opcode | fin << 7) | mask bit << 8: FrameView::hb of a send
+    __device__ uint32_t header_word0() const
+    {
+        return ((opcode() | (fin() ? 0x80u : 0u)) & 0xffu) | (mask() ? 0x100u : 0u);
+    }
 };
 
 __device__ __forceinline__ DescWords load_desc(const cfws_frame_desc_t* __restrict__ desc, uint32_t f)
@@ -233,7 +266,7 @@ __device__ __forceinline__ FrameView frame_view(const Pass& P, uint32_t f)
         v.src_off = d.payload_off;
         v.hb = kMode == kModeH2Wrap
                    ? (d.fin() ? 0x1u : 0u)                         // DATA flags: END_STREAM
-                   : ((d.opcode() | (d.fin() ? 0x80u : 0u)) & 0xffu) | (d.mask() ? 0x100u : 0u);
+                   : d.header_word0();
     } else {
         const bool ctl = is_control(d.opcode());
         const bool take = P.klass == kClassAll || (P.klass == kClassControl) == ctl;
@@ -1686,93 +1719,6 @@ __device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t x, uint64_t* s
     return before + inc - x;
 }
 
-__global__ void __launch_bounds__(kThreads)
-scan_reduce_kernel(const uint64_t* __restrict__ vals, uint64_t n, uint64_t* __restrict__ partials)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t b0 = uint64_t(blockIdx.x) * kScanBlock;
-    uint64_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        const uint64_t i = b0 + uint64_t(k) * kThreads + threadIdx.x;
-        if (i < n) sum += vals[i];
-    }
-    uint64_t total;
-    block_exclusive_scan(sum, s_wave, &total);
-    if (threadIdx.x == 0) partials[blockIdx.x] = total;
-}
-
-// One workgroup's exclusive scan of nb block sums, in place; *grand gets the
-// total. A step takes kThreads x kPartialItems sums, kPartialItems
-// consecutive ones per thread with all their loads in flight: the 16,384
-// sums of a 4 M-frame plan in one step, 19 us (one sum per thread per step:
-// 64 dependent steps, 46 us; 16 per thread through LDS with coalesced loads
-// and stores: 4 steps, 29-35 us -- each step's round trip costs more than
-// the strided access).
-constexpr int kPartialItems = 64;
-
-__device__ __forceinline__ void scan_partials_block(uint64_t* __restrict__ partials, uint64_t nb,
-                                                    uint64_t* __restrict__ grand, uint64_t* s_wave)
-{
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < nb; b += uint64_t(kThreads) * kPartialItems) {
-        const uint64_t i0 = b + uint64_t(threadIdx.x) * kPartialItems;
-        uint64_t v[kPartialItems];
-        uint64_t sum = 0;
-#pragma unroll
-        for (int k = 0; k < kPartialItems; ++k) {
-            v[k] = i0 + k < nb ? partials[i0 + k] : 0;
-            sum += v[k];
-        }
-        uint64_t tot;
-        uint64_t run = block_exclusive_scan(sum, s_wave, &tot) + carry;
-#pragma unroll
-        for (int k = 0; k < kPartialItems; ++k) {
-            if (i0 + k < nb) partials[i0 + k] = run;
-            run += v[k];
-        }
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *grand = carry;
-}
-
-__global__ void __launch_bounds__(kThreads)
-scan_partials_kernel(uint64_t* __restrict__ partials, uint64_t nb, uint64_t* __restrict__ grand)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    scan_partials_block(partials, nb, grand, s_wave);
-}
-
-// scan_partials_kernel for up to two passes in one launch (block p: pass p).
-__global__ void __launch_bounds__(kThreads)
-scan_partials2_kernel(uint64_t* __restrict__ partials0, uint64_t* __restrict__ partials1, uint64_t nb,
-                      uint64_t* __restrict__ grand0, uint64_t* __restrict__ grand1)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    scan_partials_block(blockIdx.x ? partials1 : partials0, nb, blockIdx.x ? grand1 : grand0, s_wave);
-}
-
-__global__ void __launch_bounds__(kThreads)
-scan_apply_kernel(uint64_t* __restrict__ vals, uint64_t n, const uint64_t* __restrict__ partials)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t i0 = uint64_t(blockIdx.x) * kScanBlock + uint64_t(threadIdx.x) * kScanItems;
-    uint64_t v[kScanItems];
-    uint64_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        v[k] = (i0 + k < n) ? vals[i0 + k] : 0;
-        sum += v[k];
-    }
-    uint64_t tot;
-    uint64_t run = block_exclusive_scan(sum, s_wave, &tot) + partials[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        if (i0 + k < n) vals[i0 + k] = run;
-        run += v[k];
-    }
-}
-
 // Fills the region -> first-frame map of one pass over [0, total).
 __device__ __forceinline__ void map_regions(const uint64_t* __restrict__ offs, uint64_t f, uint64_t n,
                                             uint64_t grand, uint64_t total, uint32_t* __restrict__ map)
@@ -1876,80 +1822,6 @@ __device__ __forceinline__ void ser_epilogue(uint64_t* hdr, uint64_t* user_total
 // serialize_plan_reduce_kernel two VGPRs).
 __device__ __forceinline__ uint64_t ser_wire_bytes(uint32_t hs, uint64_t len) { return hs + len; }
 
-// Offsets into the descriptors, the capacity rule, region maps, totals.
-__global__ void __launch_bounds__(kThreads)
-deserialize_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, int32_t* __restrict__ status,
-                              uint64_t* __restrict__ vals0, uint64_t* __restrict__ vals1, uint64_t n,
-                              const uint64_t* __restrict__ partials0,
-                              const uint64_t* __restrict__ partials1, uint64_t nb,
-                              uint32_t self_scan, uint64_t* __restrict__ hdr,
-                              uint64_t capacity, uint32_t reassemble, uint32_t* __restrict__ map0,
-                              uint32_t* __restrict__ map1, uint64_t* __restrict__ user_total)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    uint64_t pre0, pre1 = 0, g0, g1 = 0;
-    if (self_scan) {
-        prefix_from_partials(partials0, nb, blockIdx.x, s_wave, pre0, g0);
-        if (reassemble) prefix_from_partials(partials1, nb, blockIdx.x, s_wave, pre1, g1);
-    } else {
-        pre0 = partials0[blockIdx.x];
-        g0 = hdr[3];
-        if (reassemble) {
-            pre1 = partials1[blockIdx.x];
-            g1 = hdr[4];
-        }
-    }
-    const uint64_t t0 = g0 < capacity ? g0 : capacity;
-    const uint64_t room1 = capacity - t0;
-    const uint64_t t1 = g1 < room1 ? g1 : room1;
-    const uint64_t i0 = uint64_t(blockIdx.x) * kPlanBlock + uint64_t(threadIdx.x) * kPlanItems;
-    uint64_t v0[kPlanItems], v1[kPlanItems];
-    uint64_t s0 = 0, s1 = 0;
-#pragma unroll
-    for (int k = 0; k < kPlanItems; ++k) {
-        v0[k] = (i0 + k < n) ? vals0[i0 + k] : 0;
-        v1[k] = (reassemble && i0 + k < n) ? vals1[i0 + k] : 0;
-        s0 += v0[k];
-        s1 += v1[k];
-    }
-    uint64_t tot;
-    uint64_t run0 = block_exclusive_scan(s0, s_wave, &tot) + pre0;
-    uint64_t run1 = 0;
-    if (reassemble) run1 = block_exclusive_scan(s1, s_wave, &tot) + pre1;
-#pragma unroll
-    for (int k = 0; k < kPlanItems; ++k) {
-        const uint64_t f = i0 + k;
-        if (f < n) {
-            vals0[f] = run0;
-            const bool ctl = reassemble && is_control(desc[f].opcode);
-            const uint64_t off = ctl ? g0 + run1 : run0;
-            desc[f].payload_off = off;
-            const int32_t st = status[f];
-            if (de_capacity_rule(st, desc[f].payload_size, off, capacity) != st)
-                status[f] = CFWS_ERROR_OUT_OF_MEMORY;
-            map_range(run0, run0 + v0[k], f, t0, map0);
-            if (reassemble) {
-                vals1[f] = run1;
-                map_range(run1, run1 + v1[k], f, t1, map1);
-            }
-            if (f == n - 1) {
-                map0[(t0 + kRegion - 1) / kRegion] = (uint32_t)f;
-                if (reassemble) map1[(t1 + kRegion - 1) / kRegion] = (uint32_t)f;
-                hdr[0] = t0;
-                hdr[1] = t1;
-                hdr[2] = t0;
-                if (self_scan) {
-                    hdr[3] = g0;
-                    if (reassemble) hdr[4] = g1;
-                }
-                if (user_total) *user_total = t0 + t1;
-            }
-        }
-        run0 += v0[k];
-        run1 += v1[k];
-    }
-}
-
 // ---------------------------------------------------------------------------
 // host-side launch helpers
 // ---------------------------------------------------------------------------
@@ -1985,15 +1857,6 @@ template <typename T>
 T* ws_ptr(const void* ws, uint64_t off)
 {
     return reinterpret_cast<T*>(static_cast<char*>(const_cast<void*>(ws)) + off);
-}
-
-inline int run_scan(uint64_t* vals, uint64_t n, uint64_t* partials, uint64_t* grand, hipStream_t st)
-{
-    const uint32_t nb = grid_for(n, kScanBlock);
-    scan_reduce_kernel<<<nb, kThreads, 0, st>>>(vals, n, partials);
-    scan_partials_kernel<<<1, kThreads, 0, st>>>(partials, nb, grand);
-    scan_apply_kernel<<<nb, kThreads, 0, st>>>(vals, n, partials);
-    return launch_check("scan");
 }
 
 inline bool misaligned(const void* a, const void* b)

@@ -2,8 +2,9 @@
 // cfws_deserialize_plan): reduce / (scan) / apply launches,
 // above kSelfScanBlocks blocks one single-pass kernel with a decoupled
 // look-back, and that kernel's fused form, which also copies its frames
-// (cfws_deserialize_batch). The layout rows and
-// deserialize_plan_apply_kernel (HTTP/2 launches it too) are in cfws_kernels.h.
+// (cfws_deserialize_batch). The layout rows are in cfws_kernels.h. The scan
+// kernels and deserialize_plan_apply_kernel, which HTTP/2 and the indexing
+// launch too, are defined here (namespace cfws_rt) and declared there.
 #include "cfws_kernels.h"
 
 namespace {
@@ -588,6 +589,178 @@ int launch_single_pass(const char* what, const WsLayout& L, void* ws, uint64_t n
 }  // namespace
 
 namespace cfws_rt {
+
+// ---- the kernels other units launch too (declared in cfws_kernels.h) --------
+
+__global__ void __launch_bounds__(kThreads)
+scan_reduce_kernel(const uint64_t* __restrict__ vals, uint64_t n, uint64_t* __restrict__ partials)
+{
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t b0 = uint64_t(blockIdx.x) * kScanBlock;
+    uint64_t sum = 0;
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) {
+        const uint64_t i = b0 + uint64_t(k) * kThreads + threadIdx.x;
+        if (i < n) sum += vals[i];
+    }
+    uint64_t total;
+    block_exclusive_scan(sum, s_wave, &total);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+// One workgroup's exclusive scan of nb block sums, in place; *grand gets the
+// total. A step takes kThreads x kPartialItems sums, kPartialItems
+// consecutive ones per thread with all their loads in flight: the 16,384
+// sums of a 4 M-frame plan in one step, 19 us (one sum per thread per step:
+// 64 dependent steps, 46 us; 16 per thread through LDS with coalesced loads
+// and stores: 4 steps, 29-35 us -- each step's round trip costs more than
+// the strided access).
+constexpr int kPartialItems = 64;
+
+__device__ __forceinline__ void scan_partials_block(uint64_t* __restrict__ partials, uint64_t nb,
+                                                    uint64_t* __restrict__ grand, uint64_t* s_wave)
+{
+    uint64_t carry = 0;
+    for (uint64_t b = 0; b < nb; b += uint64_t(kThreads) * kPartialItems) {
+        const uint64_t i0 = b + uint64_t(threadIdx.x) * kPartialItems;
+        uint64_t v[kPartialItems];
+        uint64_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < kPartialItems; ++k) {
+            v[k] = i0 + k < nb ? partials[i0 + k] : 0;
+            sum += v[k];
+        }
+        uint64_t tot;
+        uint64_t run = block_exclusive_scan(sum, s_wave, &tot) + carry;
+#pragma unroll
+        for (int k = 0; k < kPartialItems; ++k) {
+            if (i0 + k < nb) partials[i0 + k] = run;
+            run += v[k];
+        }
+        carry += tot;
+    }
+    if (threadIdx.x == 0) *grand = carry;
+}
+
+__global__ void __launch_bounds__(kThreads)
+scan_partials_kernel(uint64_t* __restrict__ partials, uint64_t nb, uint64_t* __restrict__ grand)
+{
+    __shared__ uint64_t s_wave[kWaves];
+    scan_partials_block(partials, nb, grand, s_wave);
+}
+
+__global__ void __launch_bounds__(kThreads)
+scan_partials2_kernel(uint64_t* __restrict__ partials0, uint64_t* __restrict__ partials1, uint64_t nb,
+                      uint64_t* __restrict__ grand0, uint64_t* __restrict__ grand1)
+{
+    __shared__ uint64_t s_wave[kWaves];
+    scan_partials_block(blockIdx.x ? partials1 : partials0, nb, blockIdx.x ? grand1 : grand0, s_wave);
+}
+
+__global__ void __launch_bounds__(kThreads)
+scan_apply_kernel(uint64_t* __restrict__ vals, uint64_t n, const uint64_t* __restrict__ partials)
+{
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t i0 = uint64_t(blockIdx.x) * kScanBlock + uint64_t(threadIdx.x) * kScanItems;
+    uint64_t v[kScanItems];
+    uint64_t sum = 0;
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) {
+        v[k] = (i0 + k < n) ? vals[i0 + k] : 0;
+        sum += v[k];
+    }
+    uint64_t tot;
+    uint64_t run = block_exclusive_scan(sum, s_wave, &tot) + partials[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) {
+        if (i0 + k < n) vals[i0 + k] = run;
+        run += v[k];
+    }
+}
+
+int run_scan(uint64_t* vals, uint64_t n, uint64_t* partials, uint64_t* grand, hipStream_t st)
+{
+    const uint32_t nb = grid_for(n, kScanBlock);
+    scan_reduce_kernel<<<nb, kThreads, 0, st>>>(vals, n, partials);
+    scan_partials_kernel<<<1, kThreads, 0, st>>>(partials, nb, grand);
+    scan_apply_kernel<<<nb, kThreads, 0, st>>>(vals, n, partials);
+    return launch_check("scan");
+}
+
+__global__ void __launch_bounds__(kThreads)
+deserialize_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, int32_t* __restrict__ status,
+                              uint64_t* __restrict__ vals0, uint64_t* __restrict__ vals1, uint64_t n,
+                              const uint64_t* __restrict__ partials0,
+                              const uint64_t* __restrict__ partials1, uint64_t nb,
+                              uint32_t self_scan, uint64_t* __restrict__ hdr,
+                              uint64_t capacity, uint32_t reassemble, uint32_t* __restrict__ map0,
+                              uint32_t* __restrict__ map1, uint64_t* __restrict__ user_total)
+{
+    __shared__ uint64_t s_wave[kWaves];
+    uint64_t pre0, pre1 = 0, g0, g1 = 0;
+    if (self_scan) {
+        prefix_from_partials(partials0, nb, blockIdx.x, s_wave, pre0, g0);
+        if (reassemble) prefix_from_partials(partials1, nb, blockIdx.x, s_wave, pre1, g1);
+    } else {
+        pre0 = partials0[blockIdx.x];
+        g0 = hdr[3];
+        if (reassemble) {
+            pre1 = partials1[blockIdx.x];
+            g1 = hdr[4];
+        }
+    }
+    const uint64_t t0 = g0 < capacity ? g0 : capacity;
+    const uint64_t room1 = capacity - t0;
+    const uint64_t t1 = g1 < room1 ? g1 : room1;
+    const uint64_t i0 = uint64_t(blockIdx.x) * kPlanBlock + uint64_t(threadIdx.x) * kPlanItems;
+    uint64_t v0[kPlanItems], v1[kPlanItems];
+    uint64_t s0 = 0, s1 = 0;
+#pragma unroll
+    for (int k = 0; k < kPlanItems; ++k) {
+        v0[k] = (i0 + k < n) ? vals0[i0 + k] : 0;
+        v1[k] = (reassemble && i0 + k < n) ? vals1[i0 + k] : 0;
+        s0 += v0[k];
+        s1 += v1[k];
+    }
+    uint64_t tot;
+    uint64_t run0 = block_exclusive_scan(s0, s_wave, &tot) + pre0;
+    uint64_t run1 = 0;
+    if (reassemble) run1 = block_exclusive_scan(s1, s_wave, &tot) + pre1;
+#pragma unroll
+    for (int k = 0; k < kPlanItems; ++k) {
+        const uint64_t f = i0 + k;
+        if (f < n) {
+            vals0[f] = run0;
+            const bool ctl = reassemble && is_control(desc[f].opcode);
+            const uint64_t off = ctl ? g0 + run1 : run0;
+            desc[f].payload_off = off;
+            const int32_t st = status[f];
+            if (de_capacity_rule(st, desc[f].payload_size, off, capacity) != st)
+                status[f] = CFWS_ERROR_OUT_OF_MEMORY;
+            map_range(run0, run0 + v0[k], f, t0, map0);
+            if (reassemble) {
+                vals1[f] = run1;
+                map_range(run1, run1 + v1[k], f, t1, map1);
+            }
+            if (f == n - 1) {
+                map0[(t0 + kRegion - 1) / kRegion] = (uint32_t)f;
+                if (reassemble) map1[(t1 + kRegion - 1) / kRegion] = (uint32_t)f;
+                hdr[0] = t0;
+                hdr[1] = t1;
+                hdr[2] = t0;
+                if (self_scan) {
+                    hdr[3] = g0;
+                    if (reassemble) hdr[4] = g1;
+                }
+                if (user_total) *user_total = t0 + t1;
+            }
+        }
+        run0 += v0[k];
+        run1 += v1[k];
+    }
+}
+
+// ---- the deserialize plan and the fused deserialize --------------------------
 
 int deserialize_plan_impl(const void* d_wire, uint64_t wire_size, const uint64_t* d_index,
                           const uint64_t* d_ends, size_t n, uint64_t max_payload, uint32_t align,

@@ -181,6 +181,115 @@ def test_mask_packed(dev, seed):
     assert np.array_equal(got, exp)
 
 
+# header size -> (smallest payload of the class, masked); a frame of the class
+# has one of the 16 sizes from the smallest on
+HEADER_CLASSES = {2: (16, False), 6: (16, True), 4: (126, False), 8: (126, True),
+                  10: (65536, False), 14: (65536, True)}
+
+
+def packed_inrun(d, g, cap):
+    """cfws_mask_batch_packed's rule (include/cfws.h, cfws_split.hip): frame
+    g's boundary chunks are written in its first run."""
+    if g == 0:
+        return False
+    a, b = d[g - 1], d[g]
+    a_size, b_size = int(a["payload_size"]), int(b["payload_size"])
+    a_end = int(a["wire_off"]) + O.header_size(a_size, bool(a["mask"])) + a_size
+    b_dof = int(b["wire_off"]) + O.header_size(b_size, bool(b["mask"]))
+    return (a_end == int(b["wire_off"]) and a_size >= 16 and b_size >= 16
+            and (b_dof + 15) // 16 * 16 <= cap)
+
+
+def boundary_class(d, g):
+    """(hs_g, t, tph): g's header size, where its header starts in its
+    16-byte chunk, and where g - 1's last t payload bytes start in theirs."""
+    hs = O.header_size(int(d[g]["payload_size"]), bool(d[g]["mask"]))
+    t = int(d[g]["wire_off"]) % 16
+    tph = (int(d[g - 1]["payload_off"]) + int(d[g - 1]["payload_size"]) - t) % 16
+    return hs, t, tph
+
+
+def boundary_class_chain(rng, payload_len):
+    """One packed chain that meets every boundary class: a frame's size (16
+    sizes per header class) steers where the next header starts, its
+    payload_off (sources may overlap) where its own tail starts. The 64-bit
+    classes appear once per header start; then frames that must not take the
+    in-run form. Returns (desc, wire length, indices of those frames)."""
+    small = [2, 4, 6, 8]
+    targets = []                                    # (hs, t, tph) of frames 1, 2, ...
+    for t in range(16):
+        hs_of = [10, 14] + [small[(k + t) % 4] for k in range(14)]
+        targets += [(hs_of[(tph + t) % 16], t, tph) for tph in range(16)]
+    for t in range(16):                             # again on both sides of tph + t = 16
+        targets += [(small[(t + k) % 4], t, (16 - t + k) % 16) for k in range(-4, 5)]
+    rng.shuffle(targets)
+    n = 1 + len(targets)
+    d = np.zeros(n + 5, dtype=O.DESC_DTYPE)
+    off = 5                                         # frame 0: never in-run
+    plan = [(2, off % 16, 0)] + targets
+    for g in range(n):
+        hs, t, _ = plan[g]
+        lo, masked = HEADER_CLASSES[hs]
+        _, t_next, tph_next = plan[g + 1] if g + 1 < n else (0, rng.randrange(16), rng.randrange(16))
+        size = lo + (t_next - t - hs - lo) % 16
+        res = (tph_next + t_next - size) % 16
+        d[g]["payload_size"] = size
+        d[g]["payload_off"] = 16 * rng.randrange((payload_len - size - 16) // 16) + res
+        d[g]["mask"] = masked
+        d[g]["wire_off"] = off
+        assert off % 16 == t and O.header_size(size, masked) == hs
+        off += hs + size
+    # own payload 15; predecessor's payload 15; a packed frame; a 1-byte gap
+    # before a header; a packed frame
+    not_inrun = [0, n, n + 1, n + 3]
+    for g, (size, gap) in enumerate([(15, 0), (20, 0), (20, 0), (20, 1), (20, 0)], start=n):
+        masked = bool(g & 1)
+        d[g]["payload_size"] = size
+        d[g]["payload_off"] = rng.randrange(payload_len - size)
+        d[g]["mask"] = masked
+        d[g]["wire_off"] = off + gap
+        off += gap + O.header_size(size, masked) + size
+    for g in range(len(d)):
+        d[g]["fin"] = rng.random() < 0.7
+        d[g]["opcode"] = rng.choice([0, 1, 2, 8, 9])
+        d[g]["mask_key"] = rng.getrandbits(32) if d[g]["mask"] else 0
+    return d, off, not_inrun
+
+
+@pytest.mark.gpu
+def test_mask_packed_boundary_classes(dev):
+    """cfws_mask_batch_packed over every boundary class (hs_g, t, tph) of an
+    in-run frame: all 96 (header size, header start in its chunk) pairs and
+    all 256 (header start, start of the predecessor's tail in its source
+    block) pairs, which has both sides of tph + t > 16 (one source block or
+    two). Frames that must not take the in-run form sit in the same chain:
+    frame 0, a 15-byte payload and its successor, a header after a 1-byte
+    gap; and a second call cuts the capacity inside a boundary chunk.
+    Expected bytes: the oracle's encode_headers + mask_batch; bytes outside
+    the frames keep the fill."""
+    rng = random.Random(61)
+    payload = O.fill_splitmix(1 << 17, 61)
+    d, total, not_inrun = boundary_class_chain(rng, len(payload))
+    wlen = total + 21
+    inrun = [g for g in range(len(d)) if packed_inrun(d, g, wlen)]
+    classes = {boundary_class(d, g) for g in inrun}
+    assert {(hs, t) for hs, t, _ in classes} == {(hs, t) for hs in HEADER_CLASSES for t in range(16)}
+    assert {(t, tph) for _, t, tph in classes} == {(t, tph) for t in range(16) for tph in range(16)}
+    assert len(inrun) == len(d) - len(not_inrun) and not set(inrun) & set(not_inrun)
+    assert sum(int(x["payload_size"]) >= 65536 for x in d) == 32
+    # a capacity that ends inside an in-run frame's boundary chunk
+    k = next(g for g in inrun[len(inrun) // 2:]
+             if 1 <= (int(d[g]["wire_off"]) + boundary_class(d, g)[0]) % 16 <= 13)
+    cut = int(d[k]["wire_off"]) + boundary_class(d, k)[0] + 1
+    assert not packed_inrun(d, k, cut) and packed_inrun(d, k - 1, cut)
+    for cap in (wlen, cut):
+        got, _ = gpu_encode_mask(payload, d, wlen, capacity=cap, packed=True)
+        exp = np.full(wlen, 0xA5, np.uint8)
+        O.mask_batch(payload, O.encode_headers(d, exp, cap), exp, cap)
+        bad = np.nonzero(got != exp)[0]
+        assert bad.size == 0, f"cap {cap}: {bad.size} bytes differ, first at {bad[:8]}"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("max_payload", [0, 1000, 1 << 20])
 def test_mask_grid_hint(dev, max_payload):
