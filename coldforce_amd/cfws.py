@@ -29,6 +29,8 @@ ERROR_DATA_TOO_BIG = -7005
 ERROR_OUT_OF_MEMORY = -7006
 DEFAULT_MAX_PAYLOAD = 32 * 1024 * 1024          # co_ws_config.h:15
 DESERIALIZE_REASSEMBLE = 1                      # include/cfws.h
+RELAY_VERBATIM = 0                              # include/cfws.h
+RELAY_ECHO_SERVER = 1
 
 OPCODE_CONTINUATION, OPCODE_TEXT, OPCODE_BINARY = 0x0, 0x1, 0x2
 OPCODE_CLOSE, OPCODE_PING, OPCODE_PONG = 0x8, 0x9, 0xA
@@ -60,6 +62,7 @@ BATCH_SYMBOLS = (
     "cfws_index_frames", "cfws_index_workspace_size", "cfws_index_frames_batch",
     "cfws_ws_accept_keys_batch", "cfws_encode_headers", "cfws_parse_headers",
     "cfws_mask_batch", "cfws_mask_batch_packed", "cfws_unmask_batch", "cfws_copy_to_host",
+    "cfws_relay_workspace_size", "cfws_relay_batch",
     "cfws_mapped_device_pointer",
     "cfws_pipeline_set_d2h", "cfws_graph_serialize", "cfws_graph_deserialize", "cfws_graph_launch",
     "cfws_graph_destroy", "cfws_pipeline_h2_serialize", "cfws_pipeline_h2_deserialize",
@@ -134,6 +137,9 @@ def lib(path: str = LIB_PATH) -> C.CDLL:
         "cfws_mask_batch": ([_vp, _vp, _sz, _u64, _vp, _u64, _vp], C.c_int),
         "cfws_mask_batch_packed": ([_vp, _vp, _sz, _u64, _vp, _u64, _vp], C.c_int),
         "cfws_unmask_batch": ([_vp, _vp, _vp, _sz, _u64, _vp, _u64, _vp], C.c_int),
+        "cfws_relay_workspace_size": ([_sz, _u64], _sz),
+        "cfws_relay_batch": ([_vp, _u64, _vp, _sz, _u64, _u32, C.c_uint8, _vp, _vp, _vp, _vp, _u64, _vp,
+                              _vp, _sz, _vp], C.c_int),
         "cfws_copy_to_host": ([_vp, _vp, _u64, _vp], C.c_int),
         "cfws_pipeline_set_d2h": ([_vp, C.c_int], C.c_int),
         "cfws_graph_serialize": ([_vp, _vp, _sz, _vp, _u64, _vp, _vp, _sz, _vp], C.c_int),
@@ -351,6 +357,39 @@ def deserialize(wire_t, wire_size: int, index_t, payload_t, desc_t=None, status_
                                         payload_t.numel(), _p(total_t), _p(ws_t), ws_t.numel(),
                                         _stream(stream)),
            "cfws_deserialize_batch")
+    return desc_t, status_t, total_t
+
+
+def relay_workspace(n_frames: int, out_capacity: int, device="cuda"):
+    import torch
+    nbytes = lib().cfws_relay_workspace_size(n_frames, out_capacity)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def relay(wire_in_t, wire_in_size: int, index_t, wire_out_t, policy: int = RELAY_VERBATIM,
+          out_mask: bool = False, out_keys_t=None, desc_t=None, status_t=None, ws_t=None, total_t=None,
+          max_payload: int = DEFAULT_MAX_PAYLOAD, out_capacity: int | None = None, stream=None):
+    """cfws_relay_batch: the frame starting at each index_t[i] of
+    wire_in_t[:wire_in_size], when COMPLETE and emitted by `policy`, framed
+    again (out_mask, key out_keys_t[i]: uint32 / int32 tensor, None when
+    unmasked) into wire_out_t. Returns (desc_t, status_t, total_t): the parse
+    of every frame, payload_off = its outgoing frame's offset."""
+    import torch
+    n = index_t.numel()
+    dev = wire_in_t.device
+    cap = wire_out_t.numel() if out_capacity is None else out_capacity
+    if desc_t is None:
+        desc_t = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    if status_t is None:
+        status_t = torch.empty(n, dtype=torch.int32, device=dev)
+    if ws_t is None:
+        ws_t = relay_workspace(n, cap, dev)
+    if total_t is None:
+        total_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    _check(lib().cfws_relay_batch(_p(wire_in_t), wire_in_size, _p(index_t), n, max_payload, policy,
+                                  int(bool(out_mask)), _p(out_keys_t), _p(desc_t), _p(status_t),
+                                  _p(wire_out_t), cap, _p(total_t), _p(ws_t), ws_t.numel(), _stream(stream)),
+           "cfws_relay_batch")
     return desc_t, status_t, total_t
 
 

@@ -2,8 +2,9 @@
 // translation units (cfws_device.hip: WS execute / batch ABI and the
 // small-batch path; cfws_plan.hip: the WS plans and the fused deserialize;
 // cfws_slots.hip: the receive into fixed slots; cfws_h2.hip: WebSocket over
-// HTTP/2; cfws_split.hip: the split header / payload ops; cfws_ops.hip:
-// handshake keys, device indexing, copies, fills and the drop-in service).
+// HTTP/2; cfws_split.hip: the split header / payload ops; cfws_relay.hip: the
+// relay of received frames; cfws_ops.hip: handshake keys, device indexing,
+// copies, fills and the drop-in service).
 // Everything here is internal to each unit (anonymous namespace); what the
 // units share is defined once (namespace cfws_rt): the error state and the
 // pass timing in cfws_device.hip; the deserialize plan, the fused
@@ -110,7 +111,10 @@ enum : uint32_t { kClassAll = 0, kClassData = 1, kClassControl = 2 };
 //                frame: 9-byte DATA header, the WS header when the slice
 //                starts the WS frame, then the masked payload slice (one
 //                pass: the WS wire bytes are never materialised)
-enum : int { kModeSer = 0, kModeDeser = 1, kModeH2Wrap = 2, kModeH2Ser = 3 };
+//   kModeRelay:  WS relay -- per received frame that is sent on: a new header
+//                + its payload XORed with (incoming key ^ outgoing key), read
+//                from the incoming wire (cfws_relay.hip: no payload arena)
+enum : int { kModeSer = 0, kModeDeser = 1, kModeH2Wrap = 2, kModeH2Ser = 3, kModeRelay = 4 };
 __host__ __device__ constexpr bool is_ser(int mode) { return mode != kModeDeser; }
 
 // ---------------------------------------------------------------------------
@@ -221,7 +225,8 @@ struct FrameView {
     uint32_t pre;
     uint32_t hb;    // serialize: header byte 0 | mask bit << 8; DATA: flags
     uint32_t whb;   // kModeH2Ser, a WS frame's first slice: its WS header byte 0 | mask bit << 8
-    uint64_t wlen;  // kModeH2Ser, a WS frame's first slice: the WS payload size
+    uint64_t wlen;  // kModeH2Ser, a WS frame's first slice: the WS payload size;
+                    // kModeRelay: the outgoing header's key (`key` is the body's)
 };
 
 // Byte r < pre of a serialize frame's header, from its view (co_ws_frame.c:34-91).
@@ -259,6 +264,18 @@ __device__ __forceinline__ FrameView frame_view(const Pass& P, uint32_t f)
         v.key = d.key();
         v.hb = d.fin() ? 0x1u : 0u;                      // DATA flags: END_STREAM
         v.whb = d.opcode() | (d.mask() ? 0x100u : 0u);
+        v.wlen = d.wire_off;
+    } else if (kMode == kModeRelay) {
+        // one frame as relay_plan_apply_kernel laid it out: the body's offset
+        // in the incoming wire and its length, the body key (incoming ^
+        // outgoing, an unmasked side 0), the outgoing header's size (0: the
+        // frame emits nothing), its byte 0 and mask bit, and its key in the
+        // field a send does not otherwise use
+        v.pre = d.header_size();
+        v.body_len = d.payload_size;
+        v.src_off = d.payload_off;
+        v.key = d.key();
+        v.hb = d.header_word0();
         v.wlen = d.wire_off;
     } else if (is_ser(kMode)) {
         v.pre = d.header_size();
@@ -329,7 +346,8 @@ __device__ __forceinline__ void st16(uint8_t* p, uint4 o)
 // serialize gains only at 4 workgroups per CU (xform_lds_bytes), where it
 // went from 6.34-6.37 to 6.44-6.48 TB/s (at 5 per CU it lost 1-2 %;
 // profiles/r02_ab_store.txt, r02_ab_sendwt_lds.txt, r02_ab_fs.txt). The
-// HTTP/2 send keeps `nt` (write-through measured no faster there).
+// HTTP/2 send keeps `nt` (write-through measured no faster there). The relay
+// starts from serialize's policy (not measured apart).
 // CFWS_STORE_AUX_SER / _RECV override at build time.
 #ifndef CFWS_STORE_AUX_SER
 #define CFWS_STORE_AUX_SER 19
@@ -344,7 +362,7 @@ template <int kMode>
 __device__ __forceinline__ void st16_region(uint8_t* rb, uint32_t off, uint4 o)
 {
     constexpr int aux = kMode == kModeDeser ? CFWS_STORE_AUX_RECV
-                      : kMode == kModeSer ? CFWS_STORE_AUX_SER
+                      : (kMode == kModeSer || kMode == kModeRelay) ? CFWS_STORE_AUX_SER
                       : kMode == kModeH2Ser ? CFWS_STORE_AUX_H2SER : 0;
     if (aux == 0) {
         st16(rb + off, o);
@@ -404,6 +422,13 @@ __device__ __forceinline__ uint32_t header_byte_of(const Pass& P, const FrameVie
         wv.key = v.key;                                 // the first slice: rotated by 0
         wv.hb = v.whb;
         return view_header_byte(wv, r - 9u);
+    }
+    if (kMode == kModeRelay) {
+        FrameView wv;                                   // the header carries its own key
+        wv.body_len = v.body_len;
+        wv.key = (uint32_t)v.wlen;
+        wv.hb = v.hb;
+        return view_header_byte(wv, r);
     }
     return view_header_byte(v, r);
 }
@@ -546,7 +571,7 @@ __device__ __forceinline__ uint4 ws_header_words(uint64_t n, uint32_t hb, uint32
 
 // The bytes a frame writes before its body, as little-endian words (lo:
 // bytes 0-15, hi: 16-31; bytes past `pre` are don't-care):
-// * serialize: its WS header;
+// * serialize: its WS header (the relay: with the header's own key);
 // * the two-pass HTTP/2 wrap: the 9-byte DATA header (co_http2_frame.c:33-72),
 //   from constant byte indices;
 // * the fused HTTP/2 send: the DATA header, then the WS header bytes the slice
@@ -561,6 +586,7 @@ __device__ __forceinline__ HeaderWords header_words(const Pass& P, const FrameVi
 {
     const uint4 z = make_uint4(0, 0, 0, 0);
     if (kMode == kModeSer) return {ws_header_words(v.body_len, v.hb, v.key), z};
+    if (kMode == kModeRelay) return {ws_header_words(v.body_len, v.hb, (uint32_t)v.wlen), z};
     if (kMode == kModeH2Ser) {
         const uint32_t len = v.pre - 9u + (uint32_t)v.body_len;
         const uint32_t sid = P.sid & 0x7fffffffu;
@@ -1213,7 +1239,7 @@ edge_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
     P.status = status;
     P.offs = offs;
     P.total = *total_p;
-    P.capacity = capacity - out_base;
+    P.capacity = kMode == kModeRelay ? P.total : capacity - out_base;   // the relay: nothing past the total
     P.n_frames = n_frames;
     P.klass = klass;
     P.sid = sid;
@@ -1321,8 +1347,8 @@ __device__ __forceinline__ void region_loop(const Pass& P, const uint64_t* __res
     }
 }
 
-// WS serialize / deserialize and the fused WS-over-HTTP/2 send carry their
-// edge chunks in the streaming launch. The send's edge code spills 12 bytes
+// WS serialize / deserialize, the relay and the fused WS-over-HTTP/2 send
+// carry their edge chunks in the streaming launch. The send's edge code spills 12 bytes
 // per lane there (96 VGPRs, 5 waves per SIMD, the residency the LDS
 // reservation sets anyway); the spills sit in the edge branch only, none in
 // the region loop. It still measured 12 us per config-5 step faster than its
@@ -1331,7 +1357,7 @@ __device__ __forceinline__ void region_loop(const Pass& P, const uint64_t* __res
 // two-pass wrap (max_frame_size < 64) keeps a separate edge launch.
 __host__ __device__ constexpr bool has_edge_blocks(int mode)
 {
-    return mode == kModeSer || mode == kModeDeser || mode == kModeH2Ser;
+    return mode == kModeSer || mode == kModeDeser || mode == kModeH2Ser || mode == kModeRelay;
 }
 
 // The streaming kernel: serialize (kSer) = header + (masked) payload into
@@ -1390,7 +1416,9 @@ xform_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
     P.status = status;
     P.offs = offs;
     P.total = *total_p;                              // clamped by the plan
-    P.capacity = capacity - out_base;
+    // the relay writes nothing past its total (a chunk's bytes between the
+    // total and a larger capacity stay as they were)
+    P.capacity = kMode == kModeRelay ? P.total : capacity - out_base;
     P.n_frames = n_frames;
     P.klass = klass;
     P.sid = sid;
@@ -1940,7 +1968,9 @@ ArgCheck check_execute(size_t n, uint64_t cap, const void* d_payload, const void
 // serialize runs best at 4 per CU (CFWS_SER_LDS = 40000): 6.44-6.48 TB/s on
 // config 2, and ahead at every uniform frame size from 16 KiB to 1 MiB
 // (6.35-6.46 against 6.00-6.37); config 3 holds its rate since the
-// small-frame regions load their frames in one round (general_region).
+// small-frame regions load their frames in one round (general_region). The
+// relay takes serialize's reservation and small-frame threshold as a starting
+// point; neither is measured for it.
 // CFWS_XFORM_LDS overrides for every mode (0 = none).
 constexpr uint32_t kXformLdsDefault = 32000;     // 5 x fits 160 KiB, 6 x does not
 
@@ -1969,7 +1999,7 @@ inline uint64_t occ_frame_max(int mode)
 {
     static const int64_t v = env_knob("CFWS_OCC_FRAME_MAX", -1);
     if (v >= 0) return (uint64_t)v;
-    if (mode == kModeSer) return CFWS_OCC_FRAME_MAX_SER;
+    if (mode == kModeSer || mode == kModeRelay) return CFWS_OCC_FRAME_MAX_SER;
     if (mode == kModeDeser) return CFWS_OCC_FRAME_MAX_RECV;
     return 0;
 }
@@ -1982,7 +2012,7 @@ inline uint32_t xform_lds_bytes(int mode = -1, uint64_t frame_bytes = ~uint64_t(
     }();
     if (v >= 0) return (uint32_t)v;
     if (frame_bytes <= occ_frame_max(mode)) return 0;
-    if (mode == kModeSer) return CFWS_SER_LDS;
+    if (mode == kModeSer || mode == kModeRelay) return CFWS_SER_LDS;
     if (mode == kModeH2Ser) return CFWS_H2SER_LDS;
     return kXformLdsDefault;
 }

@@ -295,6 +295,61 @@ int cfws_unmask_batch(const void* d_wire, const cfws_frame_desc_t* d_desc, const
                       size_t n_frames, uint64_t max_payload_size, void* d_payload,
                       uint64_t payload_capacity, void* stream);
 
+/* ---- relay: received frames sent on in one payload pass -------------------
+ * What a server does with a frame after co_ws_frame_deserialize: the echo
+ * server sends every TEXT / BINARY / CONTINUATION frame back with
+ * co_ws_send(ws_client, fin, opcode, data, size) (examples/ws_server/main.c
+ * :54-71) and hands every other opcode to co_ws_default_handler
+ * (co_ws_client.c:563-600), which answers a PING with co_ws_send_pong on the
+ * same payload (:586-591, :552-560). co_ws_send (co_ws_client.c:428-460) is
+ * co_ws_frame_serialize with mask = !is_server. cfws_deserialize_batch +
+ * cfws_serialize_batch do that in two payload passes through a payload arena;
+ * cfws_relay_batch does it in one: out[k] = in[k] ^ key_in[k % 4] ^
+ * key_out[k % 4], read from the incoming wire.
+ *
+ * For i = 0..n_frames-1 in order: co_ws_frame_deserialize's header decisions
+ * at d_frame_index[i] against wire_in_size, exactly as cfws_parse_headers
+ * takes them (co_ws_frame.c:131-213, with the callers' 2-byte precheck,
+ * co_ws_client.c:202-206). If the frame is COMPLETE and `policy` emits it,
+ * co_ws_frame_serialize(fin', opcode', out_mask, payload) (co_ws_frame.c
+ * :34-97) with key d_out_keys[i] is appended to one byte array: d_wire_out.
+ *   CFWS_RELAY_VERBATIM     every COMPLETE frame, with its own fin and opcode.
+ *   CFWS_RELAY_ECHO_SERVER  opcodes 0, 1, 2 with their own fin and opcode
+ *     (examples/ws_server/main.c:56-62); opcode 9 as fin = 1, opcode 0xA, same
+ *     payload (co_ws_client.c:586-591, :552-560); every other opcode emits
+ *     nothing -- CLOSE and PONG stay the host's job, which finds them in
+ *     d_desc / d_status.
+ *   Any other policy: CFWS_ERROR_INVALID_ARGUMENT.
+ * d_out_keys is indexed by the input frame i and holds keys in wire order, as
+ * cfws_frame_desc_t.mask_key; it may be NULL when out_mask == 0.
+ * d_desc[i] / d_status[i] are what cfws_parse_headers writes (wire_off = the
+ * start, the incoming key, fin, opcode, mask, header_size, payload_size),
+ * except payload_off: the offset in d_wire_out where frame i's outgoing frame
+ * starts, i.e. the exclusive prefix sum of the outgoing bytes of frames
+ * 0..i-1, written for frames that emit nothing too. There is no capacity
+ * status. Bytes at or past out_capacity are not written (nor any byte past
+ * the total); *d_out_total (optional) is the unclamped total, as
+ * cfws_serialize_* reports it.
+ * Indices may repeat and come in any order (a repeated index is the fan-out
+ * of one frame). d_wire_in is readable up to round16(wire_in_size); arenas
+ * are 16-byte aligned; input and output ranges that overlap are
+ * CFWS_ERROR_INVALID_ARGUMENT. Frame-count and size limits are those of
+ * cfws_deserialize_plan / cfws_serialize_plan. Nothing is allocated, nothing
+ * synchronises. The workspace is cfws_workspace_size(n_frames, out_capacity)
+ * plus a 32-byte internal descriptor per frame
+ * (cfws_relay_workspace_size: a pure host function). */
+#define CFWS_RELAY_VERBATIM     0u
+#define CFWS_RELAY_ECHO_SERVER  1u
+
+size_t cfws_relay_workspace_size(size_t n_frames, uint64_t out_capacity);
+
+int cfws_relay_batch(const void* d_wire_in, uint64_t wire_in_size,
+                     const uint64_t* d_frame_index, size_t n_frames, uint64_t max_payload,
+                     uint32_t policy, uint8_t out_mask, const uint32_t* d_out_keys,
+                     cfws_frame_desc_t* d_desc, int32_t* d_status,
+                     void* d_wire_out, uint64_t out_capacity, uint64_t* d_out_total,
+                     void* d_workspace, size_t workspace_size, void* stream);
+
 /* ---- receive-buffer frame indexing --------
  * The frame walk of the receive loops co_ws_server_on_tcp_receive_ready
  * (co_ws_server.c:107-169) / co_ws_client_on_tcp_receive_ready
