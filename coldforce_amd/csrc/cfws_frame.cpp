@@ -29,6 +29,7 @@
 #include "cfws_co_ws_frame.h"
 #include "cfws_devpolicy.h"
 #include "cfws_internal.h"
+#include "cfws_rules.h"
 
 namespace {
 
@@ -616,7 +617,7 @@ bool co_ws_frame_serialize(bool fin, uint8_t opcode, bool mask, const void* data
                            co_byte_array_t* buffer)
 {
     const size_t start = buffer->count;
-    const size_t hmax = 2 + (n > 0xffffu ? 8 : (n > 125u ? 2 : 0)) + (mask ? 4 : 0);
+    const size_t hmax = header_size_of(n, mask);
     // The reference's only failure is malloc(n) before any key draw
     // (co_ws_frame.c:74-80); reserving up front fails at the same point.
     if (!byte_array_reserve(buffer, start + hmax + n)) return false;

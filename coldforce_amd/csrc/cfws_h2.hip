@@ -11,134 +11,13 @@
 
 namespace {
 
-// Offsets into the descriptors, the capacity rule (a COMPLETE frame with a
-// payload that does not fit gets CFWS_ERROR_OUT_OF_MEMORY, like the
-// reference's failed malloc, co_ws_frame.c:216-223), region maps.
-__global__ void __launch_bounds__(kThreads)
-deserialize_finalize_kernel(cfws_frame_desc_t* __restrict__ desc, int32_t* __restrict__ status,
-                            const uint64_t* __restrict__ offs0, const uint64_t* __restrict__ offs1,
-                            uint64_t* __restrict__ hdr, uint64_t n, uint64_t capacity,
-                            uint32_t reassemble, uint32_t* __restrict__ map0,
-                            uint32_t* __restrict__ map1, uint64_t* __restrict__ user_total)
-{
-    const uint64_t f = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (f >= n) return;
-    const uint64_t g0 = hdr[3];
-    const uint64_t g1 = reassemble ? hdr[4] : 0;
-    const uint64_t t0 = g0 < capacity ? g0 : capacity;
-    const uint64_t room1 = capacity - t0;
-    const uint64_t t1 = g1 < room1 ? g1 : room1;
-    const bool ctl = reassemble && is_control(desc[f].opcode);
-    const uint64_t off = ctl ? g0 + offs1[f] : offs0[f];
-    desc[f].payload_off = off;
-    const uint64_t len = desc[f].payload_size;
-    if (status[f] == CFWS_PARSE_COMPLETE && len > 0 && off + len > capacity)
-        status[f] = CFWS_ERROR_OUT_OF_MEMORY;
-    map_regions(offs0, f, n, g0, t0, map0);
-    if (reassemble) map_regions(offs1, f, n, g1, t1, map1);
-    if (f == n - 1) {
-        hdr[0] = t0;
-        hdr[1] = t1;
-        hdr[2] = t0;
-        if (user_total) *user_total = t0 + t1;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// WebSocket over HTTP/2 (src/ws_http2): DATA-frame wrap and unwrap
-// ---------------------------------------------------------------------------
-
-// DATA frames a serialized WS frame becomes: co_http2_stream_send_data splits
-// its bytes into frames of at most max_frame_size (co_http2_stream.c:964-1010).
-__global__ void __launch_bounds__(kThreads)
-h2_count_kernel(const cfws_frame_desc_t* __restrict__ desc, uint64_t n, uint64_t S,
-                uint64_t* __restrict__ vals)
-{
-    const uint64_t f = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (f >= n) return;
-    const uint64_t W = desc[f].header_size + desc[f].payload_size;
-    vals[f] = W <= S ? 1 : (W + S - 1) / S;
-}
-
-// One DATA-frame descriptor per slice: payload_off = slice start in the WS
-// wire arena, payload_size = slice length, fin = END_STREAM (last slice;
-// co_ws_http2_extension.c:190-194 sends every WS frame with end_stream).
-// Output offset of DATA frame d = 9 d + its wire offset.
-__global__ void __launch_bounds__(kThreads)
-h2_expand_kernel(const cfws_frame_desc_t* __restrict__ desc, const uint64_t* __restrict__ first,
-                 uint64_t n, uint64_t S, uint64_t n_max, cfws_frame_desc_t* __restrict__ ddesc,
-                 uint64_t* __restrict__ doffs)
-{
-    const uint64_t f = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (f >= n) return;
-    const uint64_t W = desc[f].header_size + desc[f].payload_size;
-    const uint64_t w0 = desc[f].wire_off;
-    const uint64_t k = W <= S ? 1 : (W + S - 1) / S;
-    for (uint64_t j = 0; j < k; ++j) {
-        const uint64_t d = first[f] + j;
-        if (d >= n_max) break;
-        cfws_frame_desc_t e;
-        e.payload_off = w0 + j * S;
-        e.wire_off = 9 * d + e.payload_off;
-        e.payload_size = (j + 1 < k) ? S : W - j * S;
-        e.mask_key = (uint32_t)f;                    // the WS frame (kModeH2Ser)
-        e.fin = (j + 1 == k) ? 1 : 0;
-        e.opcode = 0;
-        e.mask = 0;
-        e.header_size = 9;
-        ddesc[d] = e;
-        doffs[d] = e.wire_off;
-    }
-}
-
-// Unused descriptor slots past the real DATA-frame count become empty frames
-// at the end; then the region map of the wrapped arena.
-__global__ void __launch_bounds__(kThreads)
-h2_finalize_kernel(cfws_frame_desc_t* __restrict__ ddesc, uint64_t* __restrict__ doffs,
-                   uint64_t n_max, const uint64_t* __restrict__ n_data_p,
-                   const uint64_t* __restrict__ wire_total_p, uint64_t capacity,
-                   uint32_t* __restrict__ map, uint64_t* __restrict__ hdr,
-                   uint64_t* __restrict__ user_total)
-{
-    const uint64_t d = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (d >= n_max) return;
-    const uint64_t nd = *n_data_p;
-    const uint64_t T = *wire_total_p + 9 * nd;
-    const uint64_t total = T < capacity ? T : capacity;
-    if (d >= nd) {
-        cfws_frame_desc_t e = {};
-        e.payload_off = 0;
-        e.wire_off = T;
-        ddesc[d] = e;
-        doffs[d] = T;
-    }
-    const uint64_t lo = d < nd ? doffs[d] : T;
-    const uint64_t hi = d + 1 < nd ? doffs[d + 1] : T;
-    const uint64_t a = lo < total ? lo : total, b = hi < total ? hi : total;
-    if (b > a) {
-        const uint64_t r1 = (b + kRegion - 1) / kRegion;
-        for (uint64_t r = (a + kRegion - 1) / kRegion; r < r1; ++r) map[r] = (uint32_t)d;
-    }
-    if (d == n_max - 1) {
-        map[(total + kRegion - 1) / kRegion] = (uint32_t)(n_max - 1);
-        hdr[0] = total;
-        if (user_total) *user_total = T;
-    }
-}
-
 // ---- HTTP/2 send plan in two launches --------------------------------------
 // The WS layout (header sizes, wire offsets: as serialize_plan_*) and the
-// DATA frames each WS frame becomes (co_http2_stream.c:964-1010) from two
-// sums per block, wire bytes W and DATA-frame count K. The apply kernel scans
-// both, writes the WS descriptors' offsets, expands its frames' DATA
-// descriptors, maps their regions and fills the unused descriptor slots: the
-// work of serialize_plan + h2_count + a scan + h2_expand + h2_finalize (seven
-// launches) in two.
-__device__ __forceinline__ uint64_t data_frames_of(uint64_t W, uint64_t S)
-{
-    return W <= S ? 1 : (W + S - 1) / S;
-}
-
+// DATA frames each WS frame becomes (data_frames_of) from two sums per block,
+// wire bytes W and DATA-frame count K. The apply kernel scans both, writes
+// the WS descriptors' offsets, expands its frames' DATA descriptors, maps
+// their regions and fills the unused descriptor slots. Both forms of the send
+// plan this way; they differ in the descriptor the pass reads (h2_data_desc).
 __global__ void __launch_bounds__(kThreads)
 h2_ser_plan_reduce_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t n, uint64_t S,
                           uint64_t* __restrict__ partials_w, uint64_t* __restrict__ partials_k,
@@ -164,11 +43,50 @@ h2_ser_plan_reduce_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t n, uint
     }
 }
 
+// The descriptor of one DATA frame, as the send pass of kForm reads it: the
+// slice [s0, s0 + len) of the wire bytes of WS frame wd (header size hs, wire
+// offset w0), `last` the frame's last slice (END_STREAM:
+// co_ws_http2_extension.c:190-194 sends every WS frame with end_stream).
+template <int kForm>
+__device__ __forceinline__ cfws_frame_desc_t h2_data_desc(const DescWords& wd, uint64_t hs, uint64_t w0,
+                                                          uint64_t s0, uint64_t len, bool last)
+{
+    cfws_frame_desc_t e;
+    if constexpr (kForm == kModeH2Ser) {
+        // frame_view<kModeH2Ser>: h_in of the slice's bytes are WS header;
+        // body source offset and length, key rotated to the body's first
+        // payload index, bytes before the body (9 + h_in), END_STREAM; for
+        // the first slice (h_in > 0: with S >= 64 the whole WS header,
+        // s0 = 0) the WS header's fields: payload size in wire_off, byte 0
+        // in opcode, the mask bit
+        const uint64_t h_in = s0 < hs ? (hs - s0 < len ? hs - s0 : len) : 0;
+        const uint64_t q = s0 + h_in - hs;           // payload index of the body start
+        e.payload_off = wd.payload_off + q;
+        e.wire_off = h_in ? wd.payload_size : 0;
+        e.payload_size = len - h_in;
+        e.mask_key = wd.mask() ? rotr8(wd.key(), (uint32_t)(q & 3u)) : 0u;
+        e.fin = last ? 1 : 0;
+        e.opcode = h_in ? (uint8_t)((wd.opcode() | (wd.fin() ? 0x80u : 0u)) & 0xffu) : 0;
+        e.mask = h_in && wd.mask() ? 1 : 0;
+        e.header_size = (uint8_t)(9 + h_in);
+    } else {
+        // frame_view<kModeH2Wrap>: the slice's offset in the WS wire arena,
+        // its length, END_STREAM, the 9 bytes before it; nothing else is read
+        static_assert(kForm == kModeH2Wrap, "the send pass is kModeH2Ser or kModeH2Wrap");
+        e = {};
+        e.payload_off = w0 + s0;
+        e.payload_size = len;
+        e.fin = last ? 1 : 0;
+        e.header_size = 9;
+    }
+    return e;
+}
+
 // hdr[0] = DATA-stream bytes clamped by the capacity, hdr[3] = DATA frames;
 // hdr[4] / hdr[5] = the grand sums when a scan launch made them (more than
-// kSelfScanBlocks blocks). DATA frame d of WS frame f: a slice of its wire
-// bytes at 9 d + wire offset (h2_expand_kernel's output layout); its
-// descriptor holds what the send pass reads per region (see the loop).
+// kSelfScanBlocks blocks). DATA frame d of WS frame f, slice j: output offset
+// 9 d + wire offset + j S (doffs[d]).
+template <int kForm>
 __global__ void __launch_bounds__(kThreads)
 h2_ser_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t n, uint64_t S,
                          const uint64_t* __restrict__ partials_w, const uint64_t* __restrict__ partials_k,
@@ -179,15 +97,7 @@ h2_ser_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t n, uint6
 {
     __shared__ uint64_t s_wave[kWaves];
     uint64_t pre_w, pre_k, gw, gk;
-    if (self_scan) {
-        prefix_from_partials(partials_w, nb, blockIdx.x, s_wave, pre_w, gw);
-        prefix_from_partials(partials_k, nb, blockIdx.x, s_wave, pre_k, gk);
-    } else {
-        pre_w = partials_w[blockIdx.x];
-        pre_k = partials_k[blockIdx.x];
-        gw = hdr[4];
-        gk = hdr[5];
-    }
+    plan_prefix(partials_w, partials_k, nb, self_scan, hdr + 4, hdr + 5, 1u, s_wave, pre_w, gw, pre_k, gk);
     const uint64_t T = gw + 9 * gk;                      // DATA-stream bytes, unclamped
     const uint64_t total = T < capacity ? T : capacity;
     const uint64_t f = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
@@ -207,33 +117,14 @@ h2_ser_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t n, uint6
         for (uint64_t j = 0; j < k; ++j) {
             const uint64_t d = d0 + j;
             if (d >= n_max) break;
-            // DATA frame d: slice [s0, s0 + len) of WS frame f's wire bytes,
-            // h_in of them header; stored as the send pass reads it
-            // (frame_view<kModeH2Ser>): body source offset and length, key
-            // rotated to the body's first payload index, bytes before the
-            // body (9 + h_in), END_STREAM; for the first slice (h_in > 0:
-            // with S >= 64 the whole WS header, s0 = 0) the WS header's
-            // fields: payload size in wire_off, byte 0 in opcode, the mask
-            // bit (the output offset is doffs[d])
             const uint64_t s0 = j * S;
             const uint64_t len = (j + 1 < k) ? S : w - s0;
-            const uint64_t h_in = s0 < hs ? (hs - s0 < len ? hs - s0 : len) : 0;
-            const uint64_t q = s0 + h_in - hs;           // payload index of the body start
-            cfws_frame_desc_t e;
-            e.payload_off = wd.payload_off + q;
-            e.wire_off = h_in ? wd.payload_size : 0;
-            e.payload_size = len - h_in;
-            e.mask_key = wd.mask() ? rotr8(wd.key(), (uint32_t)(q & 3u)) : 0u;
-            e.fin = (j + 1 == k) ? 1 : 0;
-            e.opcode = h_in ? (uint8_t)((wd.opcode() | (wd.fin() ? 0x80u : 0u)) & 0xffu) : 0;
-            e.mask = h_in && wd.mask() ? 1 : 0;
-            e.header_size = (uint8_t)(9 + h_in);
-            ddesc[d] = e;
+            ddesc[d] = h2_data_desc<kForm>(wd, hs, w0, s0, len, j + 1 == k);
             const uint64_t out = 9 * d + w0 + s0;
             doffs[d] = out;
-            // the send's in-region edge chunks need every DATA frame but the
-            // stream's last to span a region and more (two_frame_region)
-            if (9 + len < kRegion + 32 && d + 1 < gk) atomicOr(inreg_flag, 1u);
+            // the fused send's in-region edge chunks need every DATA frame but
+            // the stream's last to span a region and more (two_frame_region)
+            if (kForm == kModeH2Ser && 9 + len < kRegion + 32 && d + 1 < gk) atomicOr(inreg_flag, 1u);
             // DATA frames lie back to back: this one ends where d + 1 starts
             map_range(out, out + 9 + len, d, total, map);
         }
@@ -253,45 +144,27 @@ h2_ser_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t n, uint6
     }
 }
 
-// HTTP/2 frame header at index[i] (co_http2_frame.c:211-300): MORE_DATA under
-// 9 bytes, PARSE_ERROR when length > max_frame_size, MORE_DATA when the
-// payload is incomplete; DATA payload after the optional pad length byte and
-// without the padding. Non-DATA frames are CFWS_H2_NOT_DATA (no bytes).
+// The DATA frame at index[i] as a descriptor: h2_frame_at's decision, with
+// type in opcode, END_STREAM in fin and the frame's offset in wire_off.
 __device__ __forceinline__ int32_t parse_h2_frame(const uint8_t* __restrict__ h2, uint64_t size,
                                                   uint64_t s, uint64_t max_frame, cfws_frame_desc_t& d)
 {
+    const H2Frame r = h2_frame_at(h2, size, s, max_frame);
     d = {};
     d.wire_off = s;
-    int32_t st = CFWS_H2_PARSE_COMPLETE;
-    do {
-        if (s > size || size - s < 9) { st = CFWS_H2_PARSE_MORE_DATA; break; }
-        const uint64_t len = (uint64_t)h2[s] << 16 | (uint64_t)h2[s + 1] << 8 | h2[s + 2];
-        if (len > max_frame) { st = CFWS_H2_PARSE_ERROR; break; }
-        if (size - s - 9 < len) { st = CFWS_H2_PARSE_MORE_DATA; break; }
-        const uint32_t type = h2[s + 3], flags = h2[s + 4];
-        d.opcode = (uint8_t)type;
-        d.fin = (uint8_t)(flags & 0x1u);
-        if (type != 0) { st = CFWS_H2_NOT_DATA; break; }
-        uint64_t pad = 0, hs = 9;
-        if (flags & 0x8u) {                               // PADDED
-            if (len < 1) { st = CFWS_H2_PARSE_ERROR; break; }
-            pad = h2[s + 9];
-            hs = 10;
-            if (pad + 1 > len) { st = CFWS_H2_PARSE_ERROR; break; }
-        }
-        d.header_size = (uint8_t)hs;
-        d.payload_size = len - (hs - 9) - pad;
-    } while (0);
-    return st;
+    d.opcode = r.type;
+    d.fin = r.end_stream;
+    d.header_size = r.header_size;
+    d.payload_size = r.payload_size;
+    return r.status;
 }
 
 // ---- HTTP/2 receive plan, fast form: two launches --------------------------
 // Valid when the pool capacity holds every DATA payload (then no frame is
 // OUT_OF_MEMORY and every COMPLETE END_STREAM frame closes a message); the
 // host checks the pooled total afterwards and otherwise runs the general
-// form (h2_parse + scans + finalize + message kernels). Reduce: the DATA
-// headers (co_http2_frame.c:211-300) and per-block sums of pooled bytes and
-// END_STREAM frames.
+// form (below). Reduce: the DATA headers and per-block sums of pooled bytes
+// and END_STREAM frames.
 __global__ void __launch_bounds__(kThreads)
 h2_de_plan_reduce_kernel(const uint8_t* __restrict__ h2, uint64_t size, const uint64_t* __restrict__ index,
                          uint64_t n, uint64_t max_frame, cfws_frame_desc_t* __restrict__ desc,
@@ -335,15 +208,7 @@ h2_de_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, const int32_t* __r
 {
     __shared__ uint64_t s_wave[kWaves];
     uint64_t pre_p, pre_e, gp, ge;
-    if (self_scan) {
-        prefix_from_partials(partials_p, nb, blockIdx.x, s_wave, pre_p, gp);
-        prefix_from_partials(partials_e, nb, blockIdx.x, s_wave, pre_e, ge);
-    } else {
-        pre_p = partials_p[blockIdx.x];
-        pre_e = partials_e[blockIdx.x];
-        gp = phdr[3];
-        ge = *n_msg_p;
-    }
+    plan_prefix(partials_p, partials_e, nb, self_scan, phdr + 3, n_msg_p, 1u, s_wave, pre_p, gp, pre_e, ge);
     // message count and pooled total straight to the caller thread's mapped
     // host words (read after one stream synchronize)
     if (host_counts && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -379,36 +244,52 @@ h2_de_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, const int32_t* __r
     }
 }
 
-// A WS message = the pooled payloads of DATA frames up to and including one
-// with END_STREAM (co_http2_stream.c:550-608). es[i] = 1 for those frames.
+// ---- HTTP/2 receive plan, general form: two launches around a scan ---------
+// The pool capacity cuts the DATA payloads. The fast form's pool offsets and
+// grand total (phdr[3]) stand. Launch one, per DATA frame: the capacity rule
+// (a frame past the capacity is OUT_OF_MEMORY), the pool pass's region map
+// and header words, and es[i] = 1 when the frame closes a message: COMPLETE
+// after the rule, with END_STREAM (co_http2_stream.c:550-608). An
+// OUT_OF_MEMORY frame closes none; an empty frame past the capacity does.
 __global__ void __launch_bounds__(kThreads)
-h2_end_flags_kernel(const cfws_frame_desc_t* __restrict__ desc, const int32_t* __restrict__ status,
-                    uint64_t n, uint64_t* __restrict__ es)
+h2_de_pool_rule_kernel(const cfws_frame_desc_t* __restrict__ desc, int32_t* __restrict__ status,
+                       const uint64_t* __restrict__ poffs, uint64_t n, uint64_t capacity,
+                       uint64_t* __restrict__ phdr, uint32_t* __restrict__ map, uint64_t* __restrict__ es)
 {
     const uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
     if (i >= n) return;
-    es[i] = (status[i] == CFWS_H2_PARSE_COMPLETE && desc[i].fin) ? 1 : 0;
+    const uint64_t g = phdr[3];
+    const uint64_t t = g < capacity ? g : capacity;
+    const uint64_t off = poffs[i], len = desc[i].payload_size;
+    int32_t st = status[i];
+    map_range(off, off + (st == CFWS_H2_PARSE_COMPLETE ? len : 0), i, t, map);
+    if (de_capacity_rule(st, len, off, capacity) != st) {
+        st = CFWS_ERROR_OUT_OF_MEMORY;
+        status[i] = st;
+    }
+    es[i] = (st == CFWS_H2_PARSE_COMPLETE && desc[i].fin) ? 1 : 0;
+    if (i == n - 1) {
+        map[(t + kRegion - 1) / kRegion] = (uint32_t)i;
+        de_epilogue(phdr, nullptr, t, g, false);
+    }
 }
 
-// Message m ends after its END_STREAM frame's data; it starts where message
-// m - 1 ended (pooled offsets are monotone, failed frames add no bytes).
+// Launch two, after the scan of es (msg_id[i] = END_STREAM frames before i):
+// the frame that closes message m ends it after its data, and m + 1 starts
+// there (pooled offsets are monotone, failed frames add no bytes).
 __global__ void __launch_bounds__(kThreads)
-h2_messages_kernel(const cfws_frame_desc_t* __restrict__ desc, const int32_t* __restrict__ status,
-                   const uint64_t* __restrict__ msg_id, uint64_t n, uint64_t* __restrict__ ends)
+h2_de_messages_kernel(const cfws_frame_desc_t* __restrict__ desc, const int32_t* __restrict__ status,
+                      const uint64_t* __restrict__ msg_id, uint64_t n, uint64_t* __restrict__ starts,
+                      uint64_t* __restrict__ ends)
 {
     const uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
     if (i >= n) return;
-    if (status[i] == CFWS_H2_PARSE_COMPLETE && desc[i].fin)
-        ends[msg_id[i]] = desc[i].payload_off + desc[i].payload_size;
-}
-
-__global__ void __launch_bounds__(kThreads)
-h2_starts_kernel(const uint64_t* __restrict__ ends, const uint64_t* __restrict__ n_msg_p,
-                 uint64_t n, uint64_t* __restrict__ starts)
-{
-    const uint64_t m = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (m >= n || m >= *n_msg_p) return;
-    starts[m] = m == 0 ? 0 : ends[m - 1];
+    if (i == 0) starts[0] = 0;
+    if (status[i] == CFWS_H2_PARSE_COMPLETE && desc[i].fin) {
+        const uint64_t m = msg_id[i], end = desc[i].payload_off + desc[i].payload_size;
+        ends[m] = end;
+        if (m + 1 < n) starts[m + 1] = end;
+    }
 }
 
 // ---- fused receive: WS frames read straight out of the DATA frames --------
@@ -548,6 +429,19 @@ __device__ __forceinline__ uint64_t h2_unit(const cfws_frame_desc_t* __restrict_
     return h2_unit_of(pdesc, h2_status, poff, d, in_msg, s_m, M, ms, hdr[3], u);
 }
 
+// Unit d of the payload pass: its descriptor (always COMPLETE: an empty unit
+// copies nothing), its output offset lo, and the regions of [lo, hi), hi
+// being where unit d + 1 starts.
+__device__ __forceinline__ void store_unit(cfws_frame_desc_t* __restrict__ udesc, int32_t* __restrict__ ustatus,
+                                           uint64_t* __restrict__ uoffs, uint32_t* __restrict__ umap, uint64_t d,
+                                           const cfws_frame_desc_t& u, uint64_t lo, uint64_t hi, uint64_t total)
+{
+    udesc[d] = u;
+    ustatus[d] = CFWS_PARSE_COMPLETE;
+    uoffs[d] = lo;
+    map_range(lo, hi, d, total, umap);
+}
+
 // One thread per DATA frame: its unit, and the region map of the payload
 // pass (a unit ends where unit d + 1 starts, computed here too, so no
 // second launch reads uoffs). *pass_total: the payload pass's total, or 0
@@ -571,11 +465,8 @@ h2_units_kernel(const cfws_frame_desc_t* __restrict__ pdesc, const int32_t* __re
     const uint64_t hi = d + 1 < n ? h2_unit(pdesc, h2_status, poff, msg_id, d + 1, n_msg, starts, mdesc,
                                             mstatus, hdr, u1)
                                   : hdr[3];
-    udesc[d] = u;
-    ustatus[d] = CFWS_PARSE_COMPLETE;
-    uoffs[d] = lo;
     const uint64_t total = hdr[0];
-    map_range(lo, hi, d, total, map);
+    store_unit(udesc, ustatus, uoffs, map, d, u, lo, hi, total);
     if (d == n - 1) map[(total + kRegion - 1) / kRegion] = (uint32_t)(n - 1);
 }
 
@@ -609,12 +500,7 @@ h2_msg_apply_units_kernel(cfws_frame_desc_t* __restrict__ mdesc, int32_t* __rest
     static_assert(kPlanItems == 1, "one message per thread");
     __shared__ uint64_t s_wave[kWaves];
     uint64_t pre, g;
-    if (self_scan) {
-        prefix_from_partials(partials, nb, blockIdx.x, s_wave, pre, g);
-    } else {
-        pre = partials[blockIdx.x];
-        g = hdr[3];
-    }
+    plan_prefix(partials, nb, self_scan, hdr + 3, s_wave, pre, g);
     const uint64_t t = g < capacity ? g : capacity;
     const uint64_t m = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
     const uint64_t v = m < n ? vals[m] : 0;
@@ -665,10 +551,7 @@ h2_msg_apply_units_kernel(cfws_frame_desc_t* __restrict__ mdesc, int32_t* __rest
             for (uint64_t d = d0; d < d1; ++d) {
                 const uint64_t hi = d + 1 < d1 ? h2_unit_of(pdesc, h2_status, poff, d + 1, true, s_m, M, ms, g, u1)
                                                : next;
-                udesc[d] = u;
-                ustatus[d] = CFWS_PARSE_COMPLETE;
-                uoffs[d] = lo;
-                map_range(lo, hi, d, t, umap);
+                store_unit(udesc, ustatus, uoffs, umap, d, u, lo, hi, t);
                 lo = hi;
                 u = u1;
             }
@@ -713,20 +596,13 @@ h2_msg_apply_units_kernel(cfws_frame_desc_t* __restrict__ mdesc, int32_t* __rest
             const uint64_t lo = h2_unit_of(pdesc, h2_status, poff, d, true, s_o, Mo, mso, g, u);
             const uint64_t hi = d + 1 < d1o ? h2_unit_of(pdesc, h2_status, poff, d + 1, true, s_o, Mo, mso, g, u1)
                                             : nexto;
-            udesc[d] = u;
-            ustatus[d] = CFWS_PARSE_COMPLETE;
-            uoffs[d] = lo;
-            map_range(lo, hi, d, t, umap);
+            store_unit(udesc, ustatus, uoffs, umap, d, u, lo, hi, t);
         }
     }
     // frames in no message: empty units at the layout's end
     const uint64_t tail0 = n_msg < n ? first[n_msg] : n;
     for (uint64_t d = tail0 + m; d < n; d += uint64_t(gridDim.x) * kThreads) {
-        cfws_frame_desc_t e = {};
-        udesc[d] = e;
-        ustatus[d] = CFWS_PARSE_COMPLETE;
-        uoffs[d] = g;
-        map_range(g, g, d, t, umap);
+        store_unit(udesc, ustatus, uoffs, umap, d, cfws_frame_desc_t{}, g, g, t);
     }
     if (m == 0 && n > 0) umap[(t + kRegion - 1) / kRegion] = (uint32_t)(n - 1);
 }
@@ -748,7 +624,7 @@ struct CountWords {
 };
 
 // Devices past kCountDevices, and any entry that cannot be made, use the
-// copies (read_counts).
+// copies (h2_de_copy_counts).
 constexpr int kCountDevices = 16;
 
 // Entries are made once and never freed: a host thread borrows one per device
@@ -867,9 +743,7 @@ bool h2_inreg()
 
 struct H2SerLayout {
     uint64_t ser;        // WS serialize workspace
-    uint64_t hdr;        // [0] wrapped total (clamped) [3] DATA-frame count
-    uint64_t vals;       // u64[n]: DATA frames per WS frame -> first DATA frame
-    uint64_t partials;
+    uint64_t hdr;        // [0] wrapped total (clamped) [3] DATA-frame count [4] [5] the plan's grand sums
     uint64_t ddesc;      // cfws_frame_desc_t[n_max]
     uint64_t doffs;      // u64[n_max]
     uint64_t map;        // u32[regions + 2]
@@ -884,8 +758,6 @@ static H2SerLayout h2_ser_layout(uint64_t n, uint64_t wire_cap, uint64_t h2_cap,
     uint64_t at = align_up(ws_layout(n, wire_cap).bytes, 256);
     L.ser = 0;
     L.hdr = at; at += 256;
-    L.vals = at; at = align_up(at + 8 * n, 256);
-    L.partials = at; at = align_up(at + 8 * ((n + kScanBlock - 1) / kScanBlock + 1), 256);
     L.ddesc = at; at = align_up(at + sizeof(cfws_frame_desc_t) * L.n_max, 256);
     L.doffs = at; at = align_up(at + 8 * L.n_max, 256);
     L.map = at; at = align_up(at + 4 * (L.regions + 2), 256);
@@ -928,6 +800,225 @@ static H2DeLayout h2_de_layout(uint64_t n, uint64_t pool_cap, uint64_t payload_c
     return L;
 }
 
+// One receive call: its arguments and its workspace pointers, resolved once.
+struct H2DeCall {
+    const uint8_t* h2;
+    uint64_t h2_size;
+    const uint64_t* index;
+    uint64_t n;
+    uint32_t S;
+    int32_t* h2_status;
+    void* pool;
+    uint64_t pool_cap, max_payload;
+    uint32_t align;
+    cfws_frame_desc_t* mdesc;
+    int32_t* mstatus;
+    void* payload;
+    uint64_t payload_cap;
+    uint64_t* payload_total;
+    void* stream;
+    hipStream_t st;
+    // the pool pass's workspace (a WsLayout over the DATA frames)
+    WsLayout PL;
+    void* pws;
+    uint64_t *phdr, *poffs, *pp, *pe;
+    uint32_t* pmap;
+    cfws_frame_desc_t* pdesc;
+    uint64_t *es, *es_part, *n_msg, *pass_total, *starts, *ends, *first;
+    // the message layout's workspace (a WsLayout over the messages) and the
+    // fused payload pass's units
+    WsLayout WL;
+    void* wsd;
+    uint64_t *hdr, *offs0, *uoffs, *part0, *part1;
+    uint32_t *mmap, *umap;
+    cfws_frame_desc_t* udesc;
+    int32_t* ustatus;
+};
+
+void h2_de_resolve(H2DeCall& c, void* ws, const H2DeLayout& L)
+{
+    c.PL = ws_layout(c.n, c.pool_cap);
+    c.pws = ws_ptr<void>(ws, L.pool);
+    c.phdr = ws_ptr<uint64_t>(c.pws, c.PL.hdr);
+    c.poffs = ws_ptr<uint64_t>(c.pws, c.PL.offs[0]);
+    c.pp = ws_ptr<uint64_t>(c.pws, c.PL.partials[0]);
+    c.pe = ws_ptr<uint64_t>(c.pws, c.PL.partials[1]);
+    c.pmap = ws_ptr<uint32_t>(c.pws, c.PL.map[0]);
+    c.pdesc = ws_ptr<cfws_frame_desc_t>(ws, L.pdesc);
+    c.es = ws_ptr<uint64_t>(ws, L.es);
+    c.es_part = ws_ptr<uint64_t>(ws, L.es_part);
+    c.n_msg = ws_ptr<uint64_t>(ws, L.es_total);
+    c.pass_total = ws_ptr<uint64_t>(ws, L.pass_total);
+    c.starts = ws_ptr<uint64_t>(ws, L.starts);
+    c.ends = ws_ptr<uint64_t>(ws, L.ends);
+    c.first = ws_ptr<uint64_t>(ws, L.first);
+    c.WL = ws_layout(c.n, c.payload_cap);
+    c.wsd = ws_ptr<void>(ws, L.wsd);
+    c.hdr = ws_ptr<uint64_t>(c.wsd, c.WL.hdr);
+    c.offs0 = ws_ptr<uint64_t>(c.wsd, c.WL.offs[0]);
+    c.uoffs = ws_ptr<uint64_t>(c.wsd, c.WL.offs[1]);
+    c.part0 = ws_ptr<uint64_t>(c.wsd, c.WL.partials[0]);
+    c.part1 = ws_ptr<uint64_t>(c.wsd, c.WL.partials[1]);
+    c.mmap = ws_ptr<uint32_t>(c.wsd, c.WL.map[0]);
+    c.umap = ws_ptr<uint32_t>(c.wsd, c.WL.map[1]);
+    c.udesc = ws_ptr<cfws_frame_desc_t>(ws, L.udesc);
+    c.ustatus = ws_ptr<int32_t>(ws, L.ustatus);
+}
+
+// The checks win in this order; an empty batch needs the workspace only.
+ArgCheck check_h2_de(const H2DeCall& c, const void* ws, size_t ws_size, uint64_t ws_bytes)
+{
+    if (!ws || ws_size < ws_bytes) return {CFWS_ERROR_WORKSPACE, "workspace too small"};
+    if (c.n == 0) return kArgsOk;
+    if (!c.h2 || !c.index || !c.h2_status || !c.pool || !c.mdesc || !c.mstatus || !c.payload)
+        return {CFWS_ERROR_INVALID_ARGUMENT, "null pointer"};
+    if (c.align == 0 || (c.align & (c.align - 1)) || c.align > 4096)
+        return {CFWS_ERROR_INVALID_ARGUMENT, "align must be a power of two <= 4096"};
+    return kArgsOk;
+}
+
+// 1. The plan's fast form: DATA headers, pool offsets, messages. It assumes
+//    the pool capacity holds every DATA payload. host_counts: the calling
+//    thread's mapped words, or null.
+void h2_de_queue_plan(const H2DeCall& c, uint64_t* host_counts)
+{
+    const uint32_t nb = grid_for(c.n, kPlanBlock);
+    const uint32_t self_scan = nb <= kSelfScanBlocks ? 1u : 0u;
+    h2_de_plan_reduce_kernel<<<nb, kThreads, 0, c.st>>>(c.h2, c.h2_size, c.index, c.n, c.S, c.pdesc,
+                                                        c.h2_status, c.pp, c.pe);
+    if (!self_scan) scan_partials2_kernel<<<2, kThreads, 0, c.st>>>(c.pp, c.pe, nb, c.phdr + 3, c.n_msg);
+    h2_de_plan_apply_kernel<<<nb, kThreads, 0, c.st>>>(c.pdesc, c.h2_status, c.n, c.pp, c.pe, nb, self_scan,
+                                                       c.phdr, c.poffs, c.es, c.n_msg, c.starts, c.ends,
+                                                       c.first, host_counts);
+}
+
+// 2. Fused, queued before the host knows the message count (rows past it are
+//    empty): the pool is never written. Each message's WS header is gathered
+//    from its DATA frames and parsed against the message's own size
+//    (co_ws_http2_extension.c:134-164); then its layout, one payload-pass
+//    unit per DATA frame, and the pass. Valid when every DATA payload fits
+//    the pool capacity; otherwise the pass stores nothing (*pass_total = 0)
+//    and the general form rewrites every output after it, in stream order
+//    (the fused kernels store only inside the payload capacity).
+//    Returns the call's timed pair (cfws_time_next_pass), recorded around
+//    the pass.
+CfwsPassEvents h2_de_queue_fused(const H2DeCall& c)
+{
+    const uint32_t mb = grid_for(c.n, kPlanBlock);
+    const uint32_t m_self = mb <= kSelfScanBlocks ? 1u : 0u;
+    h2_msg_parse_kernel<<<mb, kThreads, 0, c.st>>>(c.h2, c.pdesc, c.h2_status, c.poffs, c.n, c.starts, c.ends,
+                                                  c.n_msg, c.max_payload, c.align, c.mdesc, c.mstatus,
+                                                  c.offs0, c.first, c.part0);
+    if (!m_self) scan_partials_kernel<<<1, kThreads, 0, c.st>>>(c.part0, mb, c.hdr + 3);
+    if (h2_units_merged()) {
+        h2_msg_apply_units_kernel<<<mb, kThreads, 0, c.st>>>(
+            c.mdesc, c.mstatus, c.offs0, c.n, c.part0, mb, m_self, c.hdr, c.payload_cap, c.mmap,
+            c.payload_total, c.pdesc, c.h2_status, c.poffs, c.n_msg, c.starts, c.first, c.udesc, c.ustatus,
+            c.uoffs, c.umap, c.phdr + 3, c.pool_cap, c.pass_total);
+    } else {
+        deserialize_plan_apply_kernel<<<mb, kThreads, 0, c.st>>>(
+            c.mdesc, c.mstatus, c.offs0, c.uoffs, c.n, c.part0, c.part1, mb, m_self, c.hdr, c.payload_cap, 0,
+            c.mmap, c.umap, c.payload_total);
+        h2_units_kernel<<<grid_for(c.n, kThreads), kThreads, 0, c.st>>>(
+            c.pdesc, c.h2_status, c.poffs, c.es, c.n, c.n_msg, c.starts, c.mdesc, c.mstatus, c.hdr, c.udesc,
+            c.ustatus, c.uoffs, c.umap, c.phdr + 3, c.pool_cap, c.pass_total);
+    }
+    const CfwsPassEvents timed = cfws_internal_take_pass();
+    if (timed.start) (void)hipEventRecord(static_cast<hipEvent_t>(timed.start), c.st);
+    if (c.payload_cap)
+        launch_streaming<kModeDeser>(c.h2, c.payload, c.udesc, c.ustatus, c.uoffs, c.umap, c.pass_total,
+                                     nullptr, c.WL.regions, c.payload_cap, c.n, kClassAll, 0, c.st);
+    if (timed.stop) (void)hipEventRecord(static_cast<hipEvent_t>(timed.stop), c.st);
+    return timed;
+}
+
+// The count hand-off: the plan writes the message count and the pooled total
+// to the thread's mapped words, and the host waits on an event recorded after
+// the plan alone, while the kernels queued behind it keep the device busy (a
+// stream synchronize here left it idle 25-46 us per call on config 5).
+// Without the words or the event, copies and a stream synchronize read them.
+int h2_de_copy_counts(const H2DeCall& c, uint64_t counts[2])
+{
+    hipError_t e = hipMemcpyAsync(&counts[0], c.n_msg, 8, hipMemcpyDeviceToHost, c.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&counts[1], c.phdr + 3, 8, hipMemcpyDeviceToHost, c.st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.st);
+    if (e != hipSuccess) return set_err(CFWS_ERROR_HIP, "h2_deserialize message count", e);
+    return CFWS_OK;
+}
+
+struct CountHandoff {
+    CountWords* cw;
+    bool event;          // recorded: the host waits on it, and the words hold the counts
+
+    // after the plan; if the event cannot be recorded the copies read the
+    // counts instead (the words are still written, and nothing reads them)
+    void record(hipStream_t st)
+    {
+        event = cw && hipEventRecord(cw->ev, st) == hipSuccess;
+        if (cw && !event) (void)hipGetLastError();
+    }
+    // an early return still lets the plan finish first: the words are the
+    // thread's, and a later call must not see this call's counts land
+    int fail(int rc) const
+    {
+        if (event) (void)hipEventSynchronize(cw->ev);
+        return rc;
+    }
+    int take(const H2DeCall& c, uint64_t counts[2]) const
+    {
+        if (!event) return h2_de_copy_counts(c, counts);
+        const hipError_t e = hipEventSynchronize(cw->ev);
+        if (e != hipSuccess) return set_err(CFWS_ERROR_HIP, "h2_deserialize message count", e);
+        const volatile uint64_t* hw = cw->h;
+        counts[0] = hw[0];
+        counts[1] = hw[1];
+        return CFWS_OK;
+    }
+};
+
+// 2'. General form: the pool capacity cuts DATA payloads, and a frame past it
+//     is OUT_OF_MEMORY and closes no message. Pool offsets and the grand
+//     total stand; the capacity rule, END_STREAM flags and messages are
+//     redone. Then the pool is materialised and each pooled message goes
+//     through co_ws_frame_deserialize against its own size
+//     (co_ws_http2_extension.c:134-164; layout-first OOM rule). `timed` is
+//     recorded again, around these passes. *n_msg: set once it is known.
+int h2_de_general(const H2DeCall& c, const CfwsPassEvents& timed, uint64_t* n_msg)
+{
+    const uint32_t nb = grid_for(c.n, kThreads);
+    h2_de_pool_rule_kernel<<<nb, kThreads, 0, c.st>>>(c.pdesc, c.h2_status, c.poffs, c.n, c.pool_cap, c.phdr,
+                                                      c.pmap, c.es);
+    if (int rc = run_scan(c.es, c.n, c.es_part, c.n_msg, c.st)) return rc;
+    h2_de_messages_kernel<<<nb, kThreads, 0, c.st>>>(c.pdesc, c.h2_status, c.es, c.n, c.starts, c.ends);
+    uint64_t counts[2] = {0, 0};
+    if (int rc = h2_de_copy_counts(c, counts)) return rc;
+    const uint64_t nm = *n_msg = counts[0];
+    // rows past the message count are empty entries, as in the fused form
+    // (which wrote its own, longer, parse into some of them)
+    if (nm < c.n) {
+        hipError_t e = hipMemsetAsync(c.mdesc + nm, 0, sizeof(cfws_frame_desc_t) * (c.n - nm), c.st);
+        if (e == hipSuccess)
+            e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.mstatus + nm), CFWS_PARSE_MORE_DATA,
+                                  c.n - nm, c.st);
+        if (e != hipSuccess) return set_err(CFWS_ERROR_HIP, "h2_deserialize empty rows", e);
+    }
+    if (timed.start) (void)hipEventRecord(static_cast<hipEvent_t>(timed.start), c.st);
+    struct StopAtExit {
+        const CfwsPassEvents& e;
+        hipStream_t st;
+        ~StopAtExit() { if (e.stop) (void)hipEventRecord(static_cast<hipEvent_t>(e.stop), st); }
+    } stop_at_exit{timed, c.st};
+    if (c.pool_cap)
+        launch_pass<kModeDeser>(c.PL, 0, c.h2, c.pool, c.pdesc, c.h2_status, c.pws, c.pool_cap, c.n, kClassAll,
+                                c.st);
+    if (int rc = deserialize_plan_impl(c.pool, c.pool_cap, c.starts, c.ends, nm, c.max_payload, c.align, 0,
+                                       c.mdesc, c.mstatus, c.payload_cap, c.payload_total, c.wsd, c.WL.bytes,
+                                       c.stream))
+        return rc;
+    return cfws_deserialize_execute(c.pool, c.mdesc, c.mstatus, nm, 0, c.payload, c.payload_cap, c.wsd,
+                                    c.stream);
+}
+
 }  // namespace
 
 size_t cfws_h2_serialize_workspace_size(size_t n, uint64_t wire_cap, uint64_t h2_cap, uint32_t S)
@@ -956,47 +1047,38 @@ int cfws_h2_serialize_batch(const void* d_payload, cfws_frame_desc_t* d_desc, si
         if (d_h2_total) (void)hipMemsetAsync(d_h2_total, 0, 8, st);
         return launch_check("h2_serialize(empty)");
     }
-    // 1. the WS frames' layout, exactly as cfws_serialize_batch lays them
-    //    out (header sizes, wire offsets into d_desc). With max_frame_size
-    //    >= 64 every WS header lies in its first DATA frame and the WS bytes
-    //    go straight into the DATA frames (kModeH2Ser, one streaming pass);
-    //    smaller limits write the WS wire first and wrap it (two passes).
+    // With max_frame_size >= 64 every WS header lies in its first DATA frame
+    // and the WS bytes go straight into the DATA frames (kModeH2Ser, one
+    // streaming pass); smaller limits write the WS wire first, exactly as
+    // cfws_serialize_batch does, and wrap it (kModeH2Wrap, two passes).
     const bool fused = S >= 64;
     const WsLayout WL = ws_layout(n, wire_cap);
+    if (!fused)
+        if (int rc = cfws_serialize_batch(d_payload, d_desc, n, d_wire, wire_cap, nullptr, ws, WL.bytes, stream))
+            return rc;
+    // the plan: WS layout (header sizes, wire offsets into d_desc, as
+    // cfws_serialize_plan writes them) + DATA frames + region map in two
+    // launches (three above kSelfScanBlocks blocks)
     uint64_t* hdr = ws_ptr<uint64_t>(ws, L.hdr);
     cfws_frame_desc_t* ddesc = ws_ptr<cfws_frame_desc_t>(ws, L.ddesc);
     uint64_t* doffs = ws_ptr<uint64_t>(ws, L.doffs);
     uint32_t* map = ws_ptr<uint32_t>(ws, L.map);
     // clear: every DATA frame but the last spans more than a region, and
-    // the send's two-frame regions write the edge chunks (kEdges)
+    // the fused send's two-frame regions write the edge chunks (kEdges)
     uint32_t* inreg = reinterpret_cast<uint32_t*>(hdr + 8);
-    if (fused) {
-        // WS layout + DATA frames + region map in two launches (three above
-        // kSelfScanBlocks blocks)
-        const uint32_t nb = grid_for(n, kPlanBlock);
-        const uint32_t self_scan = nb <= kSelfScanBlocks ? 1u : 0u;
-        uint64_t* pw = ws_ptr<uint64_t>(ws, WL.partials[0]);
-        uint64_t* pk = ws_ptr<uint64_t>(ws, WL.partials[1]);
-        h2_ser_plan_reduce_kernel<<<nb, kThreads, 0, st>>>(d_desc, n, S, pw, pk, inreg);
-        if (!self_scan) scan_partials2_kernel<<<2, kThreads, 0, st>>>(pw, pk, nb, hdr + 4, hdr + 5);
-        h2_ser_plan_apply_kernel<<<nb, kThreads, 0, st>>>(d_desc, n, S, pw, pk, nb, self_scan, hdr,
-                                                         h2_cap, L.n_max, ddesc, doffs, map, d_h2_total,
-                                                         inreg);
-    } else {
-        if (int rc = cfws_serialize_batch(d_payload, d_desc, n, d_wire, wire_cap, nullptr, ws, WL.bytes,
-                                          stream))
-            return rc;
-        // 2. their DATA frames
-        uint64_t* vals = ws_ptr<uint64_t>(ws, L.vals);
-        h2_count_kernel<<<grid_for(n, kThreads), kThreads, 0, st>>>(d_desc, n, S, vals);
-        if (int rc = run_scan(vals, n, ws_ptr<uint64_t>(ws, L.partials), hdr + 3, st)) return rc;
-        h2_expand_kernel<<<grid_for(n, kThreads), kThreads, 0, st>>>(d_desc, vals, n, S, L.n_max, ddesc,
-                                                                      doffs);
-        h2_finalize_kernel<<<grid_for(L.n_max, kThreads), kThreads, 0, st>>>(
-            ddesc, doffs, L.n_max, hdr + 3, ws_ptr<const uint64_t>(ws, WL.hdr + 24), h2_cap, map, hdr,
-            d_h2_total);
-    }
-    // 3. the DATA frames: 9-byte header + slice, one streaming pass
+    const uint32_t nb = grid_for(n, kPlanBlock);
+    const uint32_t self_scan = nb <= kSelfScanBlocks ? 1u : 0u;
+    uint64_t* pw = ws_ptr<uint64_t>(ws, WL.partials[0]);
+    uint64_t* pk = ws_ptr<uint64_t>(ws, WL.partials[1]);
+    h2_ser_plan_reduce_kernel<<<nb, kThreads, 0, st>>>(d_desc, n, S, pw, pk, inreg);
+    if (!self_scan) scan_partials2_kernel<<<2, kThreads, 0, st>>>(pw, pk, nb, hdr + 4, hdr + 5);
+    if (fused)
+        h2_ser_plan_apply_kernel<kModeH2Ser><<<nb, kThreads, 0, st>>>(
+            d_desc, n, S, pw, pk, nb, self_scan, hdr, h2_cap, L.n_max, ddesc, doffs, map, d_h2_total, inreg);
+    else
+        h2_ser_plan_apply_kernel<kModeH2Wrap><<<nb, kThreads, 0, st>>>(
+            d_desc, n, S, pw, pk, nb, self_scan, hdr, h2_cap, L.n_max, ddesc, doffs, map, d_h2_total, inreg);
+    // the DATA frames: 9-byte header + slice, one streaming pass
     if (h2_cap && fused)
         launch_streaming<kModeH2Ser>(d_payload, d_h2, ddesc, nullptr, doffs, map, hdr, nullptr,
                                      L.regions, h2_cap, L.n_max, kClassAll, stream_id, st, d_desc, true,
@@ -1016,171 +1098,49 @@ int cfws_h2_deserialize_batch(const void* d_h2, uint64_t h2_size, const uint64_t
 {
     const CfwsPassScope pass_scope;
     if (int rc = check_init()) return rc;
-    if (S == 0) S = CFWS_H2_DEFAULT_MAX_FRAME_SIZE;
+    H2DeCall c = {};
+    c.h2 = static_cast<const uint8_t*>(d_h2);
+    c.h2_size = h2_size;
+    c.index = d_h2_index;
+    c.n = n;
+    c.S = S ? S : CFWS_H2_DEFAULT_MAX_FRAME_SIZE;
+    c.h2_status = d_h2_status;
+    c.pool = d_pool;
+    c.pool_cap = pool_cap;
+    c.max_payload = max_payload;
+    c.align = align;
+    c.mdesc = d_msg_desc;
+    c.mstatus = d_msg_status;
+    c.payload = d_payload;
+    c.payload_cap = payload_cap;
+    c.payload_total = d_payload_total;
+    c.stream = stream;
+    c.st = static_cast<hipStream_t>(stream);
     const H2DeLayout L = h2_de_layout(n, pool_cap, payload_cap);
-    if (!ws || ws_size < L.bytes) return set_err(CFWS_ERROR_WORKSPACE, "workspace too small", hipSuccess);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n_messages) *n_messages = 0;
+    const ArgCheck a = check_h2_de(c, ws, ws_size, L.bytes);
+    // (an undersized workspace leaves *n_messages as it was)
+    if (n_messages && a.code != CFWS_ERROR_WORKSPACE) *n_messages = 0;
+    if (a.code) return set_err(a.code, a.what, hipSuccess);
     if (n == 0) {
-        if (d_payload_total) (void)hipMemsetAsync(d_payload_total, 0, 8, st);
+        if (d_payload_total) (void)hipMemsetAsync(d_payload_total, 0, 8, c.st);
         return launch_check("h2_deserialize(empty)");
     }
-    if (!d_h2 || !d_h2_index || !d_h2_status || !d_pool || !d_msg_desc || !d_msg_status || !d_payload)
-        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "null pointer", hipSuccess);
-    // 1. unwrap: DATA payloads pooled back to back (a prefix-strip pass).
-    //    The plan's fast form assumes the pool capacity holds them all.
-    const WsLayout PL = ws_layout(n, pool_cap);
-    void* pws = ws_ptr<void>(ws, L.pool);
-    uint64_t* phdr = ws_ptr<uint64_t>(pws, PL.hdr);
-    uint64_t* poffs = ws_ptr<uint64_t>(pws, PL.offs[0]);
-    cfws_frame_desc_t* pdesc = ws_ptr<cfws_frame_desc_t>(ws, L.pdesc);
-    uint64_t* es = ws_ptr<uint64_t>(ws, L.es);
-    uint64_t* n_msg_d = ws_ptr<uint64_t>(ws, L.es_total);
-    uint64_t* starts = ws_ptr<uint64_t>(ws, L.starts);
-    uint64_t* ends = ws_ptr<uint64_t>(ws, L.ends);
-    uint64_t* first = ws_ptr<uint64_t>(ws, L.first);
-    const uint8_t* h2 = static_cast<const uint8_t*>(d_h2);
-    if (align == 0 || (align & (align - 1)) || align > 4096)
-        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "align must be a power of two <= 4096", hipSuccess);
-    uint64_t counts[2] = {0, 0};       // messages, pooled bytes
-    CountWords* cw = count_words(stream_device(st));
-    {
-        const uint32_t nb = grid_for(n, kPlanBlock);
-        const uint32_t self_scan = nb <= kSelfScanBlocks ? 1u : 0u;
-        uint64_t* pp = ws_ptr<uint64_t>(pws, PL.partials[0]);
-        uint64_t* pe = ws_ptr<uint64_t>(pws, PL.partials[1]);
-        h2_de_plan_reduce_kernel<<<nb, kThreads, 0, st>>>(h2, h2_size, d_h2_index, n, S, pdesc,
-                                                          d_h2_status, pp, pe);
-        if (!self_scan) scan_partials2_kernel<<<2, kThreads, 0, st>>>(pp, pe, nb, phdr + 3, n_msg_d);
-        h2_de_plan_apply_kernel<<<nb, kThreads, 0, st>>>(pdesc, d_h2_status, n, pp, pe, nb, self_scan,
-                                                         phdr, poffs, es, n_msg_d, starts, ends, first,
-                                                         cw ? cw->d : nullptr);
-    }
-    // the plan's event; if it cannot be recorded, the copies below read the
-    // counts instead (the words are still written, and nothing reads them)
-    bool plan_event = false;
-    if (cw) {
-        plan_event = hipEventRecord(cw->ev, st) == hipSuccess;
-        if (!plan_event) (void)hipGetLastError();
-    }
-    // an early return below still lets the plan finish first: the words are
-    // the thread's, and a later call must not see this call's counts land
-    auto fail = [&](int rc) {
-        if (plan_event) (void)hipEventSynchronize(cw->ev);
-        return rc;
-    };
-    void* wsd = ws_ptr<void>(ws, L.wsd);
-    const WsLayout WL = ws_layout(n, payload_cap);
-    uint64_t* hdr = ws_ptr<uint64_t>(wsd, WL.hdr);
-    // 2. fused, queued before the host knows the message count (rows past it
-    //    are empty): the pool is never written. Each message's WS header is
-    //    gathered from its DATA frames and parsed against the message's own
-    //    size (co_ws_http2_extension.c:134-164); then its layout. Valid when
-    //    every DATA payload fits the pool capacity; otherwise the general
-    //    form below rewrites every output after it, in stream order (the
-    //    fused kernels store only inside the payload capacity).
-    uint64_t* offs0 = ws_ptr<uint64_t>(wsd, WL.offs[0]);
-    uint64_t* part0 = ws_ptr<uint64_t>(wsd, WL.partials[0]);
-    const uint32_t mb = grid_for(n, kPlanBlock);
-    const uint32_t m_self = mb <= kSelfScanBlocks ? 1u : 0u;
-    h2_msg_parse_kernel<<<mb, kThreads, 0, st>>>(h2, pdesc, d_h2_status, poffs, n, starts, ends, n_msg_d,
-                                                max_payload, align, d_msg_desc, d_msg_status, offs0,
-                                                first, part0);
-    if (!m_self) scan_partials_kernel<<<1, kThreads, 0, st>>>(part0, mb, hdr + 3);
-    // 3. one payload-pass unit per DATA frame, and the pass's region map
-    cfws_frame_desc_t* udesc = ws_ptr<cfws_frame_desc_t>(ws, L.udesc);
-    int32_t* ustatus = ws_ptr<int32_t>(ws, L.ustatus);
-    uint64_t* uoffs = ws_ptr<uint64_t>(wsd, WL.offs[1]);
-    uint32_t* umap = ws_ptr<uint32_t>(wsd, WL.map[1]);
-    // the pass's total, or 0 when the pool overflows (it then stores nothing;
-    // the general form below does the call's work once)
-    uint64_t* pass_total = ws_ptr<uint64_t>(ws, L.pass_total);
-    if (h2_units_merged()) {
-        h2_msg_apply_units_kernel<<<mb, kThreads, 0, st>>>(
-            d_msg_desc, d_msg_status, offs0, n, part0, mb, m_self, hdr, payload_cap,
-            ws_ptr<uint32_t>(wsd, WL.map[0]), d_payload_total, pdesc, d_h2_status, poffs, n_msg_d, starts,
-            first, udesc, ustatus, uoffs, umap, phdr + 3, pool_cap, pass_total);
-    } else {
-        deserialize_plan_apply_kernel<<<mb, kThreads, 0, st>>>(
-            d_msg_desc, d_msg_status, offs0, ws_ptr<uint64_t>(wsd, WL.offs[1]), n, part0,
-            ws_ptr<uint64_t>(wsd, WL.partials[1]), mb, m_self, hdr, payload_cap, 0,
-            ws_ptr<uint32_t>(wsd, WL.map[0]), ws_ptr<uint32_t>(wsd, WL.map[1]), d_payload_total);
-        h2_units_kernel<<<grid_for(n, kThreads), kThreads, 0, st>>>(
-            pdesc, d_h2_status, poffs, es, n, n_msg_d, starts, d_msg_desc, d_msg_status, hdr, udesc,
-            ustatus, uoffs, umap, phdr + 3, pool_cap, pass_total);
-    }
-    // the call's timed pass (cfws_time_next_pass): this fused pass, or, when
+    h2_de_resolve(c, ws, L);
+    CountHandoff hand = {count_words(stream_device(c.st)), false};
+    h2_de_queue_plan(c, hand.cw ? hand.cw->d : nullptr);
+    hand.record(c.st);
+    // the call's timed pass (cfws_time_next_pass): the fused pass, or, when
     // the pool overflows and it stores nothing, the general form's passes
-    // below (the pair is recorded again around them)
-    const CfwsPassEvents timed = cfws_internal_take_pass();
-    if (timed.start) (void)hipEventRecord(static_cast<hipEvent_t>(timed.start), st);
-    if (payload_cap)
-        launch_streaming<kModeDeser>(d_h2, d_payload, udesc, ustatus, uoffs, umap, pass_total, nullptr,
-                                     WL.regions, payload_cap, n, kClassAll, 0, st);
-    if (timed.stop) (void)hipEventRecord(static_cast<hipEvent_t>(timed.stop), st);
-    if (int rc = launch_check("h2_deserialize")) return fail(rc);
-    auto read_counts = [&]() -> int {
-        hipError_t e = hipMemcpyAsync(&counts[0], n_msg_d, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&counts[1], phdr + 3, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return set_err(CFWS_ERROR_HIP, "h2_deserialize message count", e);
-        return CFWS_OK;
-    };
-    if (plan_event) {
-        // the plan's event only: the kernels above keep the device busy while
-        // the host reads the counts (a stream synchronize here left it idle
-        // 25-46 us per call on config 5)
-        const hipError_t e = hipEventSynchronize(cw->ev);
-        if (e != hipSuccess) return set_err(CFWS_ERROR_HIP, "h2_deserialize message count", e);
-        const volatile uint64_t* hw = cw->h;
-        counts[0] = hw[0];
-        counts[1] = hw[1];
-    } else if (int rc = read_counts()) {
-        return rc;
-    }
-    if (counts[1] <= pool_cap) {
-        if (n_messages) *n_messages = (size_t)counts[0];
-        return CFWS_OK;
-    }
-    // 2'. general form: the pool capacity cuts DATA payloads, and a frame
-    //     past it is OUT_OF_MEMORY and closes no message. Pool offsets and
-    //     the grand total stand; the capacity rule, END_STREAM flags and
-    //     messages are redone (co_http2_stream.c:550-608).
-    deserialize_finalize_kernel<<<grid_for(n, kThreads), kThreads, 0, st>>>(
-        pdesc, d_h2_status, poffs, poffs, phdr, n, pool_cap, 0, ws_ptr<uint32_t>(pws, PL.map[0]),
-        ws_ptr<uint32_t>(pws, PL.map[1]), nullptr);
-    h2_end_flags_kernel<<<grid_for(n, kThreads), kThreads, 0, st>>>(pdesc, d_h2_status, n, es);
-    if (int rc = run_scan(es, n, ws_ptr<uint64_t>(ws, L.es_part), n_msg_d, st)) return rc;
-    h2_messages_kernel<<<grid_for(n, kThreads), kThreads, 0, st>>>(pdesc, d_h2_status, es, n, ends);
-    h2_starts_kernel<<<grid_for(n, kThreads), kThreads, 0, st>>>(ends, n_msg_d, n, starts);
-    if (int rc = read_counts()) return rc;
-    if (n_messages) *n_messages = (size_t)counts[0];
-    // rows past the message count are empty entries, as in the fused form
-    // (which wrote its own, longer, parse into some of them)
-    if (counts[0] < n) {
-        hipError_t e = hipMemsetAsync(d_msg_desc + counts[0], 0, sizeof(cfws_frame_desc_t) * (n - counts[0]), st);
-        if (e == hipSuccess)
-            e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_msg_status + counts[0]),
-                                  CFWS_PARSE_MORE_DATA, n - counts[0], st);
-        if (e != hipSuccess) return set_err(CFWS_ERROR_HIP, "h2_deserialize empty rows", e);
-    }
-    // 3'. each pooled message through co_ws_frame_deserialize against its
-    //     own size (co_ws_http2_extension.c:134-164), from the materialised
-    //     pool (layout-first OOM rule)
-    if (timed.start) (void)hipEventRecord(static_cast<hipEvent_t>(timed.start), st);
-    struct StopAtExit {
-        const CfwsPassEvents& e;
-        hipStream_t st;
-        ~StopAtExit() { if (e.stop) (void)hipEventRecord(static_cast<hipEvent_t>(e.stop), st); }
-    } stop_at_exit{timed, st};
-    if (pool_cap)
-        launch_pass<kModeDeser>(PL, 0, d_h2, d_pool, pdesc, d_h2_status, pws, pool_cap, n, kClassAll, st);
-    if (int rc = deserialize_plan_impl(d_pool, pool_cap, starts, ends, counts[0], max_payload, align, 0,
-                                       d_msg_desc, d_msg_status, payload_cap, d_payload_total, wsd,
-                                       WL.bytes, stream))
-        return rc;
-    return cfws_deserialize_execute(d_pool, d_msg_desc, d_msg_status, counts[0], 0, d_payload,
-                                    payload_cap, wsd, stream);
+    const CfwsPassEvents timed = h2_de_queue_fused(c);
+    if (int rc = launch_check("h2_deserialize")) return hand.fail(rc);
+    uint64_t counts[2] = {0, 0};       // messages, pooled bytes
+    if (int rc = hand.take(c, counts)) return rc;
+    uint64_t n_msg = 0;
+    int rc = CFWS_OK;
+    if (counts[1] <= pool_cap) n_msg = counts[0];
+    else rc = h2_de_general(c, timed, &n_msg);
+    if (n_messages) *n_messages = (size_t)n_msg;
+    return rc;
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 
 #include "cfws.h"
 #include "cfws_internal.h"
+#include "cfws_rules.h"
 
 // Each unit uses part of what follows.
 #pragma clang diagnostic push
@@ -160,11 +161,6 @@ WsLayout ws_layout(uint64_t n, uint64_t capacity)
 // ---------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t header_size_of(uint64_t n, bool mask)
-{
-    return 2u + (n > 65535u ? 8u : (n > 125u ? 2u : 0u)) + (mask ? 4u : 0u);
-}
-
 __device__ __forceinline__ bool is_control(uint32_t opcode)
 {
     return opcode <= 0x0fu && (opcode & 0x08u) != 0;       // co_ws_frame.h:32-34
@@ -1793,6 +1789,39 @@ __device__ __forceinline__ void prefix_from_partials(const uint64_t* __restrict_
     }
     block_exclusive_scan(xb, s_wave, &before);
     block_exclusive_scan(xa, s_wave, &all);
+}
+
+// The start of a plan's apply kernel: this block's exclusive prefix and the
+// grand total of each of the plan's sums (one, or two when `second`).
+// self_scan: from the reduce kernel's per-block sums; otherwise a scan launch
+// has turned them into prefixes and stored the totals in *grand0 / *grand1.
+// (One branch for both sums: a call per sum cost the two-sum kernels 50-60
+// instructions.)
+__device__ __forceinline__ void plan_prefix(const uint64_t* __restrict__ partials0,
+                                            const uint64_t* __restrict__ partials1, uint64_t nb,
+                                            uint32_t self_scan, const uint64_t* __restrict__ grand0,
+                                            const uint64_t* __restrict__ grand1, uint32_t second, uint64_t* s_wave,
+                                            uint64_t& before0, uint64_t& all0, uint64_t& before1, uint64_t& all1)
+{
+    if (self_scan) {
+        prefix_from_partials(partials0, nb, blockIdx.x, s_wave, before0, all0);
+        if (second) prefix_from_partials(partials1, nb, blockIdx.x, s_wave, before1, all1);
+    } else {
+        before0 = partials0[blockIdx.x];
+        all0 = *grand0;
+        if (second) {
+            before1 = partials1[blockIdx.x];
+            all1 = *grand1;
+        }
+    }
+}
+
+__device__ __forceinline__ void plan_prefix(const uint64_t* __restrict__ partials, uint64_t nb,
+                                            uint32_t self_scan, const uint64_t* __restrict__ grand,
+                                            uint64_t* s_wave, uint64_t& before, uint64_t& all)
+{
+    uint64_t none0 = 0, none1 = 0;
+    plan_prefix(partials, nullptr, nb, self_scan, grand, nullptr, 0u, s_wave, before, all, none0, none1);
 }
 
 // ---- plans: two launches each (three above kSelfScanBlocks blocks) ---------

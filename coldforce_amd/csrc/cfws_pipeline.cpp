@@ -27,6 +27,7 @@
 
 #include "cfws.h"
 #include "cfws_internal.h"
+#include "cfws_rules.h"
 
 namespace {
 
@@ -55,11 +56,6 @@ struct Slot {
     void* d_ws2 = nullptr;
     size_t ws2_size = 0;
 };
-
-uint32_t hdr_size(uint64_t n, bool mask)
-{
-    return 2u + (n > 65535u ? 8u : (n > 125u ? 2u : 0u)) + (mask ? 4u : 0u);
-}
 
 int fail(const char* what, hipError_t e = hipSuccess)
 {
@@ -202,7 +198,7 @@ int cfws_pipeline_serialize(cfws_pipeline_t* p, const void* h_payload, cfws_fram
     // plan) so that chunks can be cut by wire bytes.
     uint64_t off = 0;
     for (size_t i = 0; i < n; ++i) {
-        h_desc[i].header_size = (uint8_t)hdr_size(h_desc[i].payload_size, h_desc[i].mask != 0);
+        h_desc[i].header_size = (uint8_t)header_size_of(h_desc[i].payload_size, h_desc[i].mask != 0);
         h_desc[i].wire_off = off;
         off += h_desc[i].header_size + h_desc[i].payload_size;
     }
@@ -515,8 +511,6 @@ int cfws_pipeline_receive(cfws_pipeline_t* p, const void* h_wire, uint64_t begin
 
 namespace {
 
-uint64_t data_frames(uint64_t W, uint64_t S) { return W <= S ? 1 : (W + S - 1) / S; }
-
 // A slot's HTTP/2 resources, allocated at first use: WS wire / pool scratch,
 // message statuses, and an HTTP/2 workspace of at least ws_bytes.
 int h2_slot(cfws_pipeline* p, Slot& S, size_t ws_bytes)
@@ -538,34 +532,6 @@ int h2_slot(cfws_pipeline* p, Slot& S, size_t ws_bytes)
     return CFWS_OK;
 }
 
-// The HTTP/2 frame at s of h2[0, size) as the device parse decides it
-// (co_http2_frame.c:211-300: MORE_DATA under 9 bytes or a short payload,
-// PARSE_ERROR over max_frame_size or bad padding, NOT_DATA for other types):
-// restated here because the receive pipeline cuts its chunks where no
-// message is open. *pooled = the DATA payload bytes it adds to the pool.
-int32_t h2_frame_host(const uint8_t* h2, uint64_t size, uint64_t s, uint64_t max_frame,
-                      uint64_t* pooled, bool* end_stream)
-{
-    *pooled = 0;
-    *end_stream = false;
-    if (s > size || size - s < 9) return CFWS_H2_PARSE_MORE_DATA;
-    const uint64_t len = (uint64_t)h2[s] << 16 | (uint64_t)h2[s + 1] << 8 | h2[s + 2];
-    if (len > max_frame) return CFWS_H2_PARSE_ERROR;
-    if (size - s - 9 < len) return CFWS_H2_PARSE_MORE_DATA;
-    const uint32_t type = h2[s + 3], flags = h2[s + 4];
-    if (type != 0) return CFWS_H2_NOT_DATA;
-    uint64_t pad = 0, hs = 9;
-    if (flags & 0x8u) {                                   // PADDED
-        if (len < 1) return CFWS_H2_PARSE_ERROR;
-        pad = h2[s + 9];
-        hs = 10;
-        if (pad + 1 > len) return CFWS_H2_PARSE_ERROR;
-    }
-    *pooled = len - (hs - 9) - pad;
-    *end_stream = (flags & 0x1u) != 0;
-    return CFWS_H2_PARSE_COMPLETE;
-}
-
 }  // namespace
 
 extern "C" {
@@ -584,12 +550,12 @@ int cfws_pipeline_h2_serialize(cfws_pipeline_t* p, const void* h_payload, cfws_f
     // the WS layout (as cfws_serialize_plan) and each frame's DATA-stream bytes
     uint64_t woff = 0, total = 0;
     for (size_t f = 0; f < n; ++f) {
-        const uint32_t hs = hdr_size(h_desc[f].payload_size, h_desc[f].mask != 0);
+        const uint32_t hs = header_size_of(h_desc[f].payload_size, h_desc[f].mask != 0);
         h_desc[f].header_size = (uint8_t)hs;
         h_desc[f].wire_off = woff;
         const uint64_t W = hs + h_desc[f].payload_size;
         woff += W;
-        total += W + 9 * data_frames(W, mfs);
+        total += W + 9 * data_frames_of(W, mfs);
     }
     if (h2_total) *h2_total = total;
     const size_t ws_bytes = cfws_h2_serialize_workspace_size(p->max_frames, p->chunk + 64, p->chunk + 64,
@@ -609,7 +575,7 @@ int cfws_pipeline_h2_serialize(cfws_pipeline_t* p, const void* h_payload, cfws_f
             const uint64_t a = std::min(lo, (uint64_t)h_desc[j].payload_off);
             const uint64_t b = std::max(hi, (uint64_t)(h_desc[j].payload_off + h_desc[j].payload_size));
             const uint64_t W = h_desc[j].header_size + h_desc[j].payload_size;
-            const uint64_t H = W + 9 * data_frames(W, mfs);
+            const uint64_t H = W + 9 * data_frames_of(W, mfs);
             if (j > i && ((b - (a & ~uint64_t(15))) > p->chunk || wb + W > p->chunk || hb + H > p->chunk)) break;
             lo = a;
             hi = b;
@@ -701,11 +667,11 @@ int cfws_pipeline_h2_deserialize(cfws_pipeline_t* p, const void* h_h2, uint64_t 
         size_t j = i, best = i;
         while (j < n && j - i < p->max_frames &&
                end_of(j) - wire_lo + (j + 1 - i) * uint64_t(align - 1) <= p->chunk) {
-            uint64_t pb = 0;
-            bool es = false;
-            if (h2_frame_host(h2, h2_size, h_index[j], mfs, &pb, &es) == CFWS_H2_PARSE_COMPLETE) {
-                pooled += pb;
-                open = es ? 0 : open + pb;
+            // the frame as the device decodes it (one rule: h2_frame_at)
+            const H2Frame fr = h2_frame_at(h2, h2_size, h_index[j], mfs);
+            if (fr.status == CFWS_H2_PARSE_COMPLETE) {
+                pooled += fr.payload_size;
+                open = fr.end_stream ? 0 : open + fr.payload_size;
             }
             ++j;
             if (open == 0) {

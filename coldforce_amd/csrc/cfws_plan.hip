@@ -63,12 +63,7 @@ serialize_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, uint64_t* __re
 {
     __shared__ uint64_t s_wave[kWaves];
     uint64_t prefix, g;
-    if (self_scan) {
-        prefix_from_partials(partials, nb, blockIdx.x, s_wave, prefix, g);
-    } else {
-        prefix = partials[blockIdx.x];
-        g = hdr[3];
-    }
+    plan_prefix(partials, nb, self_scan, hdr + 3, s_wave, prefix, g);
     const uint64_t total = g < capacity ? g : capacity;
     const uint64_t i0 = uint64_t(blockIdx.x) * kPlanBlock + uint64_t(threadIdx.x) * kPlanItems;
     uint64_t v[kPlanItems];
@@ -698,17 +693,7 @@ deserialize_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, int32_t* __r
 {
     __shared__ uint64_t s_wave[kWaves];
     uint64_t pre0, pre1 = 0, g0, g1 = 0;
-    if (self_scan) {
-        prefix_from_partials(partials0, nb, blockIdx.x, s_wave, pre0, g0);
-        if (reassemble) prefix_from_partials(partials1, nb, blockIdx.x, s_wave, pre1, g1);
-    } else {
-        pre0 = partials0[blockIdx.x];
-        g0 = hdr[3];
-        if (reassemble) {
-            pre1 = partials1[blockIdx.x];
-            g1 = hdr[4];
-        }
-    }
+    plan_prefix(partials0, partials1, nb, self_scan, hdr + 3, hdr + 4, reassemble, s_wave, pre0, g0, pre1, g1);
     const uint64_t t0 = g0 < capacity ? g0 : capacity;
     const uint64_t room1 = capacity - t0;
     const uint64_t t1 = g1 < room1 ? g1 : room1;

@@ -87,12 +87,7 @@ relay_plan_apply_kernel(cfws_frame_desc_t* __restrict__ desc, const int32_t* __r
 {
     __shared__ uint64_t s_wave[kWaves];
     uint64_t prefix, g;
-    if (self_scan) {
-        prefix_from_partials(partials, nb, blockIdx.x, s_wave, prefix, g);
-    } else {
-        prefix = partials[blockIdx.x];
-        g = hdr[3];
-    }
+    plan_prefix(partials, nb, self_scan, hdr + 3, s_wave, prefix, g);
     const uint64_t total = g < capacity ? g : capacity;
     const uint64_t i0 = uint64_t(blockIdx.x) * kPlanBlock + uint64_t(threadIdx.x) * kPlanItems;
     uint64_t v[kPlanItems];

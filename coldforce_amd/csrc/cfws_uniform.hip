@@ -482,16 +482,11 @@ uint64_t small_span(uint64_t fs)
     return fs >= min2 ? 2048 : 4096;
 }
 
-uint32_t uniform_header_size(uint64_t fs, bool mask)
-{
-    return 2u + (fs > 65535u ? 8u : (fs > 125u ? 2u : 0u)) + (mask ? 4u : 0u);
-}
-
 }  // namespace
 
 extern "C" const char* cfws_serialize_uniform_pass_kernel(uint64_t fs, uint8_t mask)
 {
-    switch (uniform_route(fs, uniform_header_size(fs, mask) + fs)) {
+    switch (uniform_route(fs, header_size_of(fs, mask) + fs)) {
     case kUniformSmall: return "serialize_uniform_small_kernel";
     case kUniformGeneral: return "serialize_uniform_kernel";
     default: return "serialize_uniform_bytes_kernel";
@@ -505,7 +500,7 @@ extern "C" int cfws_serialize_uniform(const void* d_payload, const uint32_t* d_k
     const CfwsPassScope pass_scope;
     if (int rc = check_init()) return rc;
     if (fs > (1ull << 30)) return set_err(CFWS_ERROR_INVALID_ARGUMENT, "payload_size > 2^30", hipSuccess);
-    const uint32_t hs = uniform_header_size(fs, mask);
+    const uint32_t hs = header_size_of(fs, mask);
     const uint64_t W = hs + fs;
     if (n > (uint64_t(1) << 40) / W) return set_err(CFWS_ERROR_INVALID_ARGUMENT, "batch over 2^40 wire bytes",
                                                     hipSuccess);

@@ -127,24 +127,61 @@ def test_gpu_h2_serialize_random(S):
 
 @pytest.mark.gpu
 @pytest.mark.skipif(not gpu_present(), reason="needs the MI355X")
-@pytest.mark.parametrize("n", [1, 255, 256, 257, 65536, 65537, 524288, 524289])
-def test_gpu_h2_serialize_plan_grid_sizes(n):
+@pytest.mark.parametrize("n,S", [pytest.param(n, 16384, id=str(n))
+                                 for n in (1, 255, 256, 257, 65536, 65537, 524288, 524289)] +
+                                [pytest.param(n, 16, id=f"{n}-S16") for n in (256, 257, 524288, 524289)])
+def test_gpu_h2_serialize_plan_grid_sizes(n, S):
     """The send plan around its block bounds (256 frames per block; past
     2,048 blocks a scan launch between reduce and apply), called twice on
-    the same arenas."""
+    the same arenas: the fused form, and at S = 16 the two-pass form (WS wire
+    first, then the same plan with the wrap pass's descriptors)."""
     rng = np.random.default_rng(n)
     payload = O.fill_splitmix(1 << 20, 77, 0)
     d = np.zeros(n, dtype=O.DESC_DTYPE)
-    d["payload_size"] = rng.choice([0, 1, 125, 126, 3000, 16376, 20000] if n < 65536 else [0, 1, 125, 126, 300], n)
+    sizes = [0, 1, 5, 40] if S == 16 else [0, 1, 125, 126, 3000, 16376, 20000] if n < 65536 else [0, 1, 125, 126, 300]
+    d["payload_size"] = rng.choice(sizes, n)
     d["payload_off"] = rng.integers(0, (1 << 20) - 20000, n).astype(np.uint64)
     d["mask"] = (rng.random(n) < .7).astype(np.uint8)
     d["mask_key"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32) * d["mask"]
     d["fin"], d["opcode"] = 1, 2
-    exp, _ = O.h2_serialize_batch(payload, d, 3, 16384)
+    exp, _ = O.h2_serialize_batch(payload, d, 3, S)
     for _ in range(2):
-        got, t = gpu_h2_serialize(payload, d, 3, 16384)
+        got, t = gpu_h2_serialize(payload, d, 3, S)
         assert t == len(exp)
         assert np.array_equal(got, exp)
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not gpu_present(), reason="needs the MI355X")
+@pytest.mark.parametrize("S", [63, 16])
+def test_gpu_h2_serialize_two_pass_capacity_cut(S):
+    """The two-pass send (max_frame_size < 64) with the DATA-stream capacity
+    inside the stream: the returned total is the unclamped one, the bytes up
+    to the capacity are the stream's, and nothing is stored past it (as the
+    "cut" case of the fused form)."""
+    torch, cfws = _gpu()
+    from coldforce_amd import workloads as W
+    rng = random.Random(S)
+    payload = O.fill_splitmix(1 << 20, S, 0)
+    n = 300
+    d = np.zeros(n, dtype=O.DESC_DTYPE)
+    for i in range(n):
+        sz = rng.choice([0, 1, 125, 126, 999, 5000])
+        m = rng.random() < .7
+        d[i] = (rng.randrange(0, (1 << 20) - sz), 0, sz, rng.getrandbits(32) if m else 0, rng.random() < .6,
+                rng.choice([0, 1, 2, 9]), m, 0)
+    exp, _ = O.h2_serialize_batch(payload, d, 7, S)
+    pay = torch.from_numpy(payload).cuda()
+    _, wtotal = W.wire_layout(d)
+    wire = torch.empty(W.round16(wtotal) + 16, dtype=torch.uint8, device="cuda")
+    for cap in (len(exp) // 2 + 4101, len(exp) // 3 // 4096 * 4096):
+        assert 0 < cap < len(exp)
+        h2 = torch.full((cap + 4096,), 0xEE, dtype=torch.uint8, device="cuda")
+        tot = cfws.h2_serialize(pay, cfws.desc_to_device(d), wire, h2[:cap], 7, S)
+        torch.cuda.synchronize()
+        assert int(tot.item()) == len(exp)
+        got = h2.cpu().numpy()
+        assert np.array_equal(got[:cap], exp[:cap]) and (got[cap:] == 0xEE).all(), cap
 
 
 @pytest.mark.gpu
@@ -570,6 +607,42 @@ def test_gpu_h2_rows_past_message_count_are_empty(pool_div):
     for f in ("wire_off", "payload_size", "mask_key", "fin", "opcode", "mask", "header_size"):
         assert not rest[f].any(), f
     assert bool((ms[m:] == O.PARSE_MORE_DATA).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not gpu_present(), reason="needs the MI355X")
+def test_gpu_h2_empty_data_frames_past_the_pool_cut():
+    """The receive's general form where the capacity rule (len > 0) and the
+    message close meet: past the pool capacity a DATA frame with bytes is
+    OUT_OF_MEMORY and closes no message, an empty COMPLETE frame with
+    END_STREAM still does. After the cut the stream gets empty DATA frames
+    with and without END_STREAM between the frames of the messages, and one
+    whole message that is a single empty END_STREAM frame."""
+    h2, index = _h2_case(33, 60, sizes=(0, 7, 126, 1000, 20000))
+    pool_cap = len(h2) // 2
+    lens = np.array([int.from_bytes(h2[int(s):int(s) + 3].tobytes(), "big") for s in index])
+    past = np.nonzero(np.cumsum(lens) - lens > pool_cap)[0]          # frames that start past the capacity
+    assert past.size >= 12
+    # DATA header: length 0, type 0, flags, stream 1
+    empty = lambda flags: np.array([0, 0, 0, 0, flags, 0, 0, 0, 1], np.uint8)
+    closes = lambda k: bool(h2[int(index[k]) + 4] & 1)
+    mid = [int(k) for k in past[1:] if not closes(k - 1)]           # inside a message
+    new = [int(k) for k in past[1:] if closes(k - 1)]               # where a message starts
+    assert len(mid) >= 2 and len(new) >= 3
+    ins = {mid[0]: [empty(1)], mid[1]: [empty(0)], new[0]: [empty(0), empty(0)],
+           new[1]: [empty(1)],                                      # a whole message
+           new[2]: [empty(0), empty(1)]}
+    parts = []
+    for k in range(len(index)):
+        parts += ins.get(k, [])
+        parts.append(h2[int(index[k]):int(index[k]) + 9 + int(lens[k])])
+    parts += [empty(0), empty(1)]
+    h2 = np.concatenate(parts)
+    index = O.h2_index(h2)
+    assert len(index) == len(lens) + 9
+    got = check_h2_deserialize(h2, index, pool_cap=pool_cap)
+    assert (got["h2_status"] == O.ERROR_OUT_OF_MEMORY).any() and 0 < got["n_msg"] < 60 + 5
+    check_h2_deserialize(h2, index, pool_cap=pool_cap, align=1, payload_cap=pool_cap // 3)
 
 
 @pytest.mark.gpu
