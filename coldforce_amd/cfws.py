@@ -54,6 +54,8 @@ BATCH_SYMBOLS = (
     "cfws_deserialize_plan", "cfws_deserialize_execute", "cfws_deserialize_batch",
     "cfws_deserialize_slots", "cfws_deserialize_scatter", "cfws_deserialize_slots_info",
     "cfws_deserialize_scatter_info", "cfws_deserialize_slots_uniform", "cfws_xor_mask", "cfws_draw_mask_keys", "cfws_draw_mask_keys_seeded",
+    "cfws_draw_mask_keys_seeded_at", "cfws_draw_mask_keys_device", "cfws_draw_keys_workspace_size",
+    "cfws_draw_keys_group_frames",
     "cfws_release_thread_resources", "cfws_set_dropin_gpu_min", "cfws_dropin_gpu_min",
     "cfws_fill_splitmix", "cfws_pipeline_create", "cfws_pipeline_destroy",
     "cfws_pipeline_serialize", "cfws_pipeline_deserialize", "cfws_pipeline_receive",
@@ -154,6 +156,10 @@ def lib(path: str = LIB_PATH) -> C.CDLL:
         "cfws_xor_mask": ([_vp, _vp, _u64, _u32, _u32, _vp], C.c_int),
         "cfws_draw_mask_keys": ([_sz, _vp, _vp], None),
         "cfws_draw_mask_keys_seeded": ([_u32, _sz, _vp, _vp], C.c_int),
+        "cfws_draw_mask_keys_seeded_at": ([_u32, _u64, _sz, _vp, _vp, C.POINTER(_u64)], C.c_int),
+        "cfws_draw_mask_keys_device": ([_u32, _u64, _sz, _vp, _vp, _vp, _vp, _sz, _vp], C.c_int),
+        "cfws_draw_keys_workspace_size": ([_sz], _sz),
+        "cfws_draw_keys_group_frames": ([], _sz),
         "cfws_release_thread_resources": ([], None),
         "cfws_init_device": ([C.c_int], C.c_int),
         "cfws_device_copy": ([_vp, _vp, _u64, _vp], C.c_int),
@@ -245,6 +251,50 @@ def draw_mask_keys(n: int, mask_flags=None, seed: int | None = None) -> np.ndarr
         _check(lib().cfws_draw_mask_keys_seeded(seed, n, mp, keys.ctypes.data),
                "cfws_draw_mask_keys_seeded")
     return keys
+
+
+def draw_mask_keys_at(n: int, mask_flags=None, seed: int = 0, first_draw: int = 0):
+    """cfws_draw_mask_keys_seeded_at: the keys draw_mask_keys(n, mask_flags,
+    seed) would give frames that come after first_draw calls of random()
+    since srandom(seed). Returns (keys, next_draw): next_draw is the
+    first_draw of the batch that follows."""
+    keys = np.zeros(n, dtype=np.uint32)
+    mf = None if mask_flags is None else np.ascontiguousarray(mask_flags, dtype=np.uint8)
+    nxt = _u64(0)
+    _check(lib().cfws_draw_mask_keys_seeded_at(seed, first_draw, n, None if mf is None else mf.ctypes.data,
+                                               keys.ctypes.data, C.byref(nxt)), "cfws_draw_mask_keys_seeded_at")
+    return keys, int(nxt.value)
+
+
+def draw_keys_workspace_size(n: int) -> int:
+    """Bytes of workspace draw_mask_keys_device needs with mask flags."""
+    return lib().cfws_draw_keys_workspace_size(n)
+
+
+def draw_keys_group_frames() -> int:
+    """Frames one workgroup of the device draw covers."""
+    return lib().cfws_draw_keys_group_frames()
+
+
+def draw_mask_keys_device(n: int, mask_flags_t=None, seed: int = 0, first_draw: int = 0, keys_t=None,
+                          next_draw_t=None, ws_t=None, stream=None):
+    """cfws_draw_mask_keys_device: draw_mask_keys_at on the device, queued on
+    the stream. mask_flags_t: uint8 tensor readable to round16(n) bytes, or
+    None (every frame masked). keys_t (n int32, 16-byte aligned),
+    next_draw_t (one int64) and, with flags, ws_t are allocated when not
+    given. Returns (keys_t, next_draw_t)."""
+    import torch
+    dev = "cuda" if mask_flags_t is None else mask_flags_t.device
+    if keys_t is None:
+        keys_t = torch.empty(n, dtype=torch.int32, device=dev)
+    if next_draw_t is None:
+        next_draw_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    if ws_t is None and mask_flags_t is not None:
+        ws_t = torch.empty(draw_keys_workspace_size(n), dtype=torch.uint8, device=dev)
+    _check(lib().cfws_draw_mask_keys_device(seed, first_draw, n, _p(mask_flags_t), _p(keys_t), _p(next_draw_t),
+                                            _p(ws_t), 0 if ws_t is None else ws_t.numel(), _stream(stream)),
+           "cfws_draw_mask_keys_device")
+    return keys_t, next_draw_t
 
 
 def header_sizes(sizes: np.ndarray, masks: np.ndarray) -> np.ndarray:

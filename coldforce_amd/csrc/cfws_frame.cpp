@@ -29,6 +29,7 @@
 #include "cfws_co_ws_frame.h"
 #include "cfws_devpolicy.h"
 #include "cfws_internal.h"
+#include "cfws_keyrules.h"
 #include "cfws_rules.h"
 
 namespace {
@@ -751,6 +752,53 @@ int cfws_draw_mask_keys_seeded(uint32_t seed, size_t n, const uint8_t* mask_flag
         }
         keys[i] = k;
     }
+    return CFWS_OK;
+}
+
+}  // extern "C"
+
+// The generator's 31 words (mod 2^9, cfws_keyrules.h) after first_draw calls
+// of random() since srandom(seed): the table is glibc's own, taken as
+// cfws_draw_mask_keys_seeded takes it, in draw order from the front pointer;
+// the position is reached by x^first_draw mod p applied to its window.
+int cfws_internal_key_state(uint32_t seed, uint64_t first_draw, uint32_t (&h)[kKeyDeg])
+{
+    int32_t table[32];
+    struct random_data rd;
+    memset(&rd, 0, sizeof rd);
+    memset(table, 0, sizeof table);
+    if (initstate_r(seed, reinterpret_cast<char*>(table), sizeof table, &rd) != 0) return CFWS_ERROR_INVALID_ARGUMENT;
+    const int front = static_cast<int>(rd.fptr - rd.state);
+    uint32_t W[kKeyWindow], q[kKeyDeg];
+    for (int i = 0; i < kKeyDeg; ++i) W[i] = static_cast<uint32_t>(rd.state[(front + i) % kKeyDeg]) & kKeyMask;
+    key_window_extend(W);
+    key_poly_xpow(first_draw, q);
+    key_poly_apply(q, W, h);
+    return CFWS_OK;
+}
+
+extern "C" {
+
+int cfws_draw_mask_keys_seeded_at(uint32_t seed, uint64_t first_draw, size_t n, const uint8_t* mask_flags,
+                                  uint32_t* keys, uint64_t* next_draw)
+{
+    if (first_draw > kCfwsKeyMaxFirstDraw || (n != 0 && !keys)) return CFWS_ERROR_INVALID_ARGUMENT;
+    uint32_t ring[kKeyDeg];
+    if (int rc = cfws_internal_key_state(seed, first_draw, ring)) return rc;
+    uint64_t drawn = 0;
+    int at = 0;                    // drawn % 31
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t k = 0;
+        if (!mask_flags || mask_flags[i]) {
+            for (int j = 0; j < 4; ++j) {
+                k |= key_draw(ring, at) << (8 * j);
+                at = at + 1 == kKeyDeg ? 0 : at + 1;
+            }
+            drawn += 4;
+        }
+        keys[i] = k;
+    }
+    if (next_draw) *next_draw = first_draw + drawn;
     return CFWS_OK;
 }
 

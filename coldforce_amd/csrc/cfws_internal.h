@@ -51,6 +51,12 @@ struct CfwsPassTimer {
     void* stream;
 };
 
+// The key generator's 31 words mod 2^9 (cfws_keyrules.h) at draw first_draw
+// of srandom(seed)'s stream (cfws_frame.cpp; the device draw of
+// cfws_keys.hip starts from them). CFWS_OK or CFWS_ERROR_INVALID_ARGUMENT.
+constexpr uint64_t kCfwsKeyMaxFirstDraw = uint64_t(1) << 62;
+int cfws_internal_key_state(uint32_t seed, uint64_t first_draw, uint32_t (&h)[31]);
+
 // The drop-in's frame service (cfws_ops.hip, used by cfws_frame.cpp): one
 // resident workgroup per device that serves every calling thread of the
 // process. Each thread owns a slot: a request word and a done word in the

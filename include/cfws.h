@@ -571,6 +571,38 @@ void cfws_draw_mask_keys(size_t n_frames, const uint8_t* mask_flags, uint32_t* k
  * random() state is not touched. CFWS_OK, or CFWS_ERROR_INVALID_ARGUMENT. */
 int cfws_draw_mask_keys_seeded(uint32_t seed, size_t n_frames, const uint8_t* mask_flags,
                                uint32_t* keys);
+/* The same stream entered at a position: the keys cfws_draw_mask_keys_seeded
+ * (seed, ...) would give frames that come after first_draw calls of random()
+ * since srandom(seed). The masked frame of rank m (counting masked frames
+ * only) gets byte j = draw first_draw + 4 m + j; unmasked frames get 0 and
+ * draw nothing. *next_draw (may be NULL) = first_draw + 4 x masked frames:
+ * the first_draw of the batch that follows. first_draw <= 2^62, and need not
+ * be a multiple of 4 (other users of random(), such as the handshake key,
+ * move the stream by other amounts). The generator is linear, so the call
+ * jumps to the position (a few dozen 31 x 31 products) and discards
+ * nothing. first_draw = 0 is cfws_draw_mask_keys_seeded. Host memory; the
+ * process's random() state is not touched. CFWS_OK, or
+ * CFWS_ERROR_INVALID_ARGUMENT (first_draw, or keys NULL with n_frames > 0). */
+int cfws_draw_mask_keys_seeded_at(uint32_t seed, uint64_t first_draw, size_t n_frames,
+                                  const uint8_t* mask_flags, uint32_t* keys, uint64_t* next_draw);
+/* The device form: the same keys into d_keys and the same next position into
+ * *d_next_draw (device memory, may be NULL), queued on `stream`. Nothing is
+ * allocated, copied from host memory or synchronised. d_mask_flags == NULL:
+ * every frame masked, one launch, no workspace. With d_mask_flags (device,
+ * readable to round16(n_frames) bytes) the call needs d_workspace of
+ * cfws_draw_keys_workspace_size(n_frames) bytes, 16-byte aligned; its
+ * contents on entry do not matter. d_keys is 16-byte aligned and exactly
+ * 4 x n_frames bytes of it are written. n_frames < 2^32. n_frames = 0
+ * writes no key and *d_next_draw = first_draw. Not a timed pass: a pending
+ * cfws_time_next_pass pair is dropped. CFWS_OK, or
+ * CFWS_ERROR_INVALID_ARGUMENT / _WORKSPACE / _NO_DEVICE / _HIP.
+ * cfws_draw_keys_group_frames: the frames one workgroup draws (a constant of
+ * the build; the sizes at which the kernel's paths change are its multiples). */
+size_t cfws_draw_keys_workspace_size(size_t n_frames);
+int cfws_draw_mask_keys_device(uint32_t seed, uint64_t first_draw, size_t n_frames,
+                               const uint8_t* d_mask_flags, uint32_t* d_keys, uint64_t* d_next_draw,
+                               void* d_workspace, size_t workspace_size, void* stream);
+size_t cfws_draw_keys_group_frames(void);
 
 /* Frees the calling thread's drop-in staging buffers and stream
  * (cfws_frame.cpp) now; optional: a thread that exits without calling it
