@@ -7,9 +7,9 @@
 HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_ops cfws_uniform
+DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_handshake cfws_ops cfws_uniform
 HOSTSRC  := cfws_frame cfws_pipeline cfws_index cfws_graph
-HDR      := include/cfws.h include/cfws_co_ws_frame.h coldforce_amd/csrc/cfws_internal.h coldforce_amd/csrc/cfws_rules.h coldforce_amd/csrc/cfws_keyrules.h coldforce_amd/csrc/cfws_devpolicy.h
+HDR      := include/cfws.h include/cfws_co_ws_frame.h coldforce_amd/csrc/cfws_internal.h coldforce_amd/csrc/cfws_rules.h coldforce_amd/csrc/cfws_keyrules.h coldforce_amd/csrc/cfws_keydev.h coldforce_amd/csrc/cfws_devpolicy.h
 LIB      := coldforce_amd/libcfws.so
 OBJDIR   := build
 

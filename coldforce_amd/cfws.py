@@ -62,7 +62,8 @@ BATCH_SYMBOLS = (
     "cfws_h2_serialize_workspace_size", "cfws_h2_serialize_batch",
     "cfws_h2_deserialize_workspace_size", "cfws_h2_deserialize_batch",
     "cfws_index_frames", "cfws_index_workspace_size", "cfws_index_frames_batch",
-    "cfws_ws_accept_keys_batch", "cfws_encode_headers", "cfws_parse_headers",
+    "cfws_ws_accept_keys_batch", "cfws_ws_client_keys_batch", "cfws_ws_client_keys_group_conns",
+    "cfws_ws_upgrade_keys_batch", "cfws_ws_check_accept_batch", "cfws_encode_headers", "cfws_parse_headers",
     "cfws_mask_batch", "cfws_mask_batch_packed", "cfws_unmask_batch", "cfws_copy_to_host",
     "cfws_relay_workspace_size", "cfws_relay_batch",
     "cfws_mapped_device_pointer",
@@ -185,6 +186,10 @@ def lib(path: str = LIB_PATH) -> C.CDLL:
         "cfws_index_frames_batch": ([_vp, _vp, _vp, _sz, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
                                      _sz, _vp], C.c_int),
         "cfws_ws_accept_keys_batch": ([_vp, _vp, _sz, _vp, _vp], C.c_int),
+        "cfws_ws_client_keys_batch": ([_u32, _u64, _sz, _vp, _vp, _vp, _vp], C.c_int),
+        "cfws_ws_client_keys_group_conns": ([], _sz),
+        "cfws_ws_upgrade_keys_batch": ([_vp, _vp, _sz, _vp, _vp, _vp, _vp], C.c_int),
+        "cfws_ws_check_accept_batch": ([_vp, _vp, _vp, _sz, _vp, _vp, _vp], C.c_int),
         "cfws_pipeline_create": ([_u64, _sz, C.c_int, C.POINTER(_vp)], C.c_int),
         "cfws_pipeline_destroy": ([_vp], None),
         "cfws_pipeline_serialize": ([_vp, _vp, _vp, _sz, _vp, _u64, C.POINTER(_u64)], C.c_int),
@@ -920,6 +925,82 @@ def ws_accept_keys(keys, device="cuda", stream=None) -> list[str]:
                                            _stream(stream)), "cfws_ws_accept_keys_batch")
     h = out.cpu().numpy().reshape(-1, WS_ACCEPT_SLOT)
     return [bytes(h[i, :28]).decode() for i in range(len(keys))]
+
+
+# ---- the rest of the upgrade's key handling ----------------------------------
+WS_KEY_SLOT = 32
+
+
+def ws_client_keys_group_conns() -> int:
+    """Connections one workgroup of the client-key kernel produces."""
+    return lib().cfws_ws_client_keys_group_conns()
+
+
+def _slot_strings(t, n: int) -> list[str]:
+    """The NUL-terminated strings of n 32-byte slots of a device tensor."""
+    h = t[:32 * n].cpu().numpy().reshape(n, 32)
+    return [bytes(r).split(b"\0", 1)[0].decode("latin-1") for r in h]
+
+
+def _packed(items, device):
+    """Byte strings as (bytes tensor, n + 1 offsets tensor) on the device."""
+    import torch
+    off = np.zeros(len(items) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(k) for k in items])
+    raw = np.frombuffer(b"".join(items) or b"\0", np.uint8).copy()
+    return torch.from_numpy(raw).to(device), torch.from_numpy(off).to(device)
+
+
+def ws_client_keys_into(n: int, keys_t, accepts_t=None, next_draw_t=None, seed: int = 0, first_draw: int = 0,
+                        stream=None) -> None:
+    """cfws_ws_client_keys_batch into the caller's tensors: keys_t and
+    accepts_t (optional) 32 n bytes each, 16-byte aligned; next_draw_t
+    (optional) one int64. Queued on the stream."""
+    _check(lib().cfws_ws_client_keys_batch(seed, first_draw, n, _p(keys_t), _p(accepts_t), _p(next_draw_t),
+                                           _stream(stream)), "cfws_ws_client_keys_batch")
+
+
+def ws_client_keys(n: int, seed: int = 0, first_draw: int = 0, device="cuda", stream=None):
+    """The Sec-WebSocket-Key values of n sequential upgrade requests made
+    after first_draw calls of random() since srandom(seed), and the accept
+    values their answers must carry. Returns (keys, accepts, next_draw):
+    next_draw is the first_draw of whatever draws next (draw_mask_keys_device
+    for the frames those connections send)."""
+    import torch
+    keys_t = torch.zeros(max(n, 1) * WS_KEY_SLOT, dtype=torch.uint8, device=device)
+    acc_t = torch.zeros(max(n, 1) * WS_ACCEPT_SLOT, dtype=torch.uint8, device=device)
+    nxt = torch.zeros(1, dtype=torch.int64, device=device)
+    ws_client_keys_into(n, keys_t, acc_t, nxt, seed, first_draw, stream)
+    return _slot_strings(keys_t, n), _slot_strings(acc_t, n), int(nxt.item())
+
+
+def ws_upgrade_keys(keys, device="cuda", stream=None):
+    """The server's decision on every Sec-WebSocket-Key (bytes) and its
+    accept value (cfws_ws_upgrade_keys_batch). Returns (valid: uint8 array,
+    accepts: list[str], invalid: int)."""
+    import torch
+    n = len(keys)
+    d_keys, d_off = _packed(keys, device)
+    valid = torch.zeros(max(n, 1), dtype=torch.uint8, device=device)
+    out = torch.zeros(max(n, 1) * WS_ACCEPT_SLOT, dtype=torch.uint8, device=device)
+    cnt = torch.zeros(1, dtype=torch.int32, device=device)
+    _check(lib().cfws_ws_upgrade_keys_batch(_p(d_keys), _p(d_off), n, _p(valid), _p(out), _p(cnt),
+                                            _stream(stream)), "cfws_ws_upgrade_keys_batch")
+    return valid[:n].cpu().numpy(), _slot_strings(out, n), int(cnt.item())
+
+
+def ws_check_accept(expect_t, answers, stream=None):
+    """strcmp of every answer (bytes) with the expected accept value in
+    expect_t's 32-byte slots (cfws_ws_check_accept_batch). Returns
+    (ok: uint8 array, failed: int)."""
+    import torch
+    n = len(answers)
+    d_resp, d_off = _packed(answers, expect_t.device)
+    ok = torch.zeros(max(n, 1), dtype=torch.uint8, device=expect_t.device)
+    cnt = torch.zeros(1, dtype=torch.int32, device=expect_t.device)
+    _check(lib().cfws_ws_check_accept_batch(_p(expect_t), _p(d_resp), _p(d_off), n, _p(ok), _p(cnt),
+                                            _stream(stream)), "cfws_ws_check_accept_batch")
+    return ok[:n].cpu().numpy(), int(cnt.item())
 
 
 # ---- host-memory pipeline --------------------------------------------------

@@ -3,8 +3,9 @@
 // small-batch path; cfws_plan.hip: the WS plans and the fused deserialize;
 // cfws_slots.hip: the receive into fixed slots; cfws_h2.hip: WebSocket over
 // HTTP/2; cfws_split.hip: the split header / payload ops; cfws_relay.hip: the
-// relay of received frames; cfws_keys.hip: the mask-key draw; cfws_ops.hip:
-// handshake keys, device indexing, copies, fills and the drop-in service).
+// relay of received frames; cfws_keys.hip: the mask-key draw;
+// cfws_handshake.hip: the upgrade's keys and their checks; cfws_ops.hip:
+// device indexing, copies, fills and the drop-in service).
 // Everything here is internal to each unit (anonymous namespace); what the
 // units share is defined once (namespace cfws_rt): the error state and the
 // pass timing in cfws_device.hip; the deserialize plan, the fused

@@ -1,6 +1,7 @@
 // cfws_keyrules.h -- the mask-key generator's rules, written once for the
 // host form (cfws_frame.cpp: cfws_draw_mask_keys_seeded_at), the device form
-// (cfws_keys.hip) and that unit's compile-time tables.
+// (cfws_keydev.h: the entry cfws_keys.hip and cfws_handshake.hip draw from)
+// and its compile-time tables.
 //
 // The reference draws a key as four random() % 256 (co_ws_frame.c:84 ->
 // co_random.c:32-35). With h[0..30] the 31 words of the seeded table in draw

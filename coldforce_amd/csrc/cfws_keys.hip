@@ -1,102 +1,20 @@
 // cfws_keys.hip -- cfws_draw_mask_keys_device: the keys
-// cfws_draw_mask_keys_seeded_at gives, drawn on the device. The generator is
-// sequential, but linear (cfws_keyrules.h): a position k draws ahead is
-// x^k mod p applied to a 61-word window, so every lane enters the stream at
-// the start of its own run.
-//   host    the 31 words at first_draw (cfws_internal_key_state), by value;
-//   wave g  jumps by g * kWaveDraws: one application of x^(kWaveDraws 2^j)
-//           per set bit j of g, the window spread over the wave's lanes;
-//   lane l  jumps by l * kLaneDraws from the wave's window: x^(kLaneDraws l)
-//           applied with the window in scalar registers;
-//   then    kLaneDraws draws on a ring of 31 registers, every index static,
-//           stored as kLaneFrames / 4 chunks of 16 bytes: one 128-byte line.
-// Both tables of polynomials are built at compile time. With mask flags the
+// cfws_draw_mask_keys_seeded_at gives, drawn on the device. Every lane enters
+// the stream at the start of its own run (cfws_keydev.h: a wave jump, a lane
+// jump, then a ring of 31 registers) and draws kLaneDraws times, stored as
+// kLaneFrames / 4 chunks of 16 bytes: one 128-byte line. With mask flags the
 // draw goes packed into the workspace (n keys: an upper bound) and a second
 // pass ranks the masked frames and writes keys[i] = flag ? packed[rank] : 0.
 #include "cfws_kernels.h"
-#include "cfws_keyrules.h"
+#include "cfws_keydev.h"
 
 namespace {
 
-constexpr uint32_t kLaneFrames = 32;                          // r: one lane's run
+constexpr uint32_t kLaneFrames = uint32_t(kLaneDraws / 4);    // r: one lane's run
 constexpr uint32_t kWaveFrames = 64 * kLaneFrames;            // w: one wave's run
 constexpr uint32_t kGroupFrames = kWaves * kWaveFrames;       // G: one workgroup's
-constexpr uint64_t kLaneDraws = 4 * uint64_t(kLaneFrames);
-constexpr uint64_t kWaveDraws = 4 * uint64_t(kWaveFrames);
-constexpr int kWaveBits = 21;                                 // waves of a batch: n < 2^32 frames
 static_assert((uint64_t(1) << 32) / kWaveFrames <= (uint64_t(1) << kWaveBits), "wave index bits");
 static_assert(kLaneFrames % 4 == 0, "a lane's run is whole 16-byte chunks");
-
-// A polynomial mod p over Z/2^9: 31 coefficients, padded to four 16-byte loads.
-struct alignas(16) KeyPoly {
-    uint16_t c[32];
-};
-template <int N>
-struct KeyPolys {
-    KeyPoly p[N];
-};
-
-constexpr void put_poly(KeyPoly& d, const uint32_t (&q)[kKeyDeg])
-{
-    for (int i = 0; i < kKeyDeg; ++i) d.c[i] = (uint16_t)q[i];
-}
-
-// x^(kWaveDraws 2^j), j < kWaveBits
-constexpr KeyPolys<kWaveBits> wave_pows()
-{
-    KeyPolys<kWaveBits> T = {};
-    uint32_t q[kKeyDeg] = {};
-    key_poly_xpow(kWaveDraws, q);
-    for (int j = 0; j < kWaveBits; ++j) {
-        put_poly(T.p[j], q);
-        key_poly_mul(q, q, q);
-    }
-    return T;
-}
-
-// x^(kLaneDraws l), l < 64
-constexpr KeyPolys<64> lane_pows()
-{
-    KeyPolys<64> T = {};
-    uint32_t q[kKeyDeg] = {}, step[kKeyDeg] = {};
-    key_poly_xpow(0, q);
-    key_poly_xpow(kLaneDraws, step);
-    for (int l = 0; l < 64; ++l) {
-        put_poly(T.p[l], q);
-        key_poly_mul(q, step, q);
-    }
-    return T;
-}
-
-__device__ const KeyPolys<kWaveBits> kWavePow = wave_pows();
-__device__ const KeyPolys<64> kLanePow = lane_pows();
-
-struct KeyState {
-    uint32_t h[kKeyDeg];
-};
-
-// key_window_extend over lanes: lane i < 31 holds W[i]; afterwards lane
-// i < 61 holds W[i]. W[t + 31] needs W[t + 28], so three words per round.
-__device__ __forceinline__ uint32_t wave_window_extend(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t t = kKeyDeg; t < (uint32_t)kKeyWindow; t += kKeyDeg - kKeyTap) {
-        const uint32_t a = __shfl(v, (int)((lane - kKeyDeg) & 63u), 64);
-        const uint32_t b = __shfl(v, (int)((lane - (kKeyDeg - kKeyTap)) & 63u), 64);
-        if (lane >= t && lane < t + (kKeyDeg - kKeyTap)) v = key_next(a, b) & kKeyMask;
-    }
-    return v;
-}
-
-// key_poly_apply over lanes: lane j < 31 gets sum_c q[c] W[c + j] from the
-// window wave_window_extend left; q is the same for the whole wave.
-__device__ __forceinline__ uint32_t wave_poly_apply(const KeyPoly& q, uint32_t v, uint32_t lane)
-{
-    uint32_t s = 0;
-#pragma unroll
-    for (int c = 0; c < kKeyDeg; ++c) s += key_mul(q.c[c], (uint32_t)__shfl(v, (int)((lane + c) & 63u), 64));
-    return key_sum(s);
-}
 
 // Keys [0, n) of the stream whose 31 words at its first draw are `base`,
 // kGroupFrames per workgroup. keys: 16-byte aligned, written in [0, 4 n).
@@ -110,34 +28,13 @@ draw_keys_kernel(KeyState base, uint64_t n, uint32_t* __restrict__ keys, uint64_
     const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
     const uint64_t wave_first = uint64_t(g) * kWaveFrames;
     if (wave_first >= n) return;                          // whole waves only: the shuffles below need all lanes
-    uint32_t v = 0;
-#pragma unroll
-    for (int i = 0; i < kKeyDeg; ++i)
-        if (lane == (uint32_t)i) v = base.h[i];
-    for (uint32_t j = 0; (g >> j) != 0; ++j) {
-        if (!((g >> j) & 1u)) continue;
-        v = wave_poly_apply(kWavePow.p[j], wave_window_extend(v, lane), lane);
-    }
-    v = wave_window_extend(v, lane);
     uint32_t W[kKeyWindow];
-#pragma unroll
-    for (int i = 0; i < kKeyWindow; ++i) W[i] = (uint32_t)__builtin_amdgcn_readlane((int)v, i);
+    key_wave_window(base, g, lane, W);
 
     const uint64_t k0 = wave_first + uint64_t(lane) * kLaneFrames;
     if (k0 >= n) return;
-    uint32_t q[kKeyDeg], ring[kKeyDeg];
-    const uint4* qp = reinterpret_cast<const uint4*>(kLanePow.p[lane].c);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint4 w = qp[i];
-        const uint32_t d[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            q[8 * i + 2 * k] = d[k] & 0xffffu;
-            if (8 * i + 2 * k + 1 < kKeyDeg) q[8 * i + 2 * k + 1] = d[k] >> 16;
-        }
-    }
-    key_poly_apply(q, W, ring);
+    uint32_t ring[kKeyDeg];
+    key_lane_ring(W, lane, ring);
 #pragma unroll
     for (uint32_t c = 0; c < kLaneFrames / 4; ++c) {
         const uint64_t kf = k0 + 4 * c;

@@ -1,6 +1,5 @@
 // cfws_ops.hip -- the codec's smaller device operations and their C ABI
-// (include/cfws.h): handshake accept keys, the multi-connection receive
-// walk, the D2H copy into mapped host memory, the single-buffer XOR of the
+// (include/cfws.h): the multi-connection receive walk, the D2H copy into mapped host memory, the single-buffer XOR of the
 // per-frame drop-in and its frame service, the bench's plain device copy,
 // and the synthetic fill. (The split header / payload ops: cfws_split.hip.)
 #include "cfws_kernels.h"
@@ -268,150 +267,6 @@ fill_splitmix_kernel(uint8_t* __restrict__ dst, uint64_t n, uint64_t seed, uint6
 }
 
 // ---------------------------------------------------------------------------
-// handshake accept keys (co_ws_create_base64_accept_key,
-// co_ws_http_extension.c:26-57): base64(SHA-1(key || GUID))
-// ---------------------------------------------------------------------------
-__constant__ char kWsGuid[37] = "258EAFA5-E914-47DA-95CA-C5AB0DC85B11";
-__constant__ char kB64[65] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
-
-// A base64 character (RFC 4648 4, co_base64.c's table). The table lookup
-// measured 10 % faster than computing the character by compares.
-__device__ __forceinline__ uint32_t b64_char(uint32_t x) { return (uint8_t)kB64[x]; }
-
-// Byte i of the SHA-1 input key || GUID || 0x80 || 0... || bit length (BE64)
-// over `blocks` 64-byte blocks.
-__device__ __forceinline__ uint32_t accept_msg_byte(const uint8_t* __restrict__ key, uint64_t L,
-                                                    uint64_t blocks, uint64_t i)
-{
-    const uint64_t m = L + 36;
-    if (i < L) return key[i];
-    if (i < m) return (uint8_t)kWsGuid[i - L];
-    if (i == m) return 0x80u;
-    const uint64_t end = blocks * 64;
-    if (i >= end - 8) return (uint32_t)((m * 8) >> (8 * (end - 1 - i))) & 0xffu;
-    return 0;
-}
-
-__device__ __forceinline__ uint32_t rol32(uint32_t v, int b) { return (v << b) | (v >> (32 - b)); }
-
-// One SHA-1 block (80 rounds over a 16-word schedule kept in registers).
-// When w is a compile-time constant (the second block of a 24-byte key's
-// message), the whole schedule folds into constants.
-__device__ __forceinline__ void sha1_block(uint32_t (&st)[5], uint32_t (&w)[16])
-{
-    uint32_t a = st[0], bb = st[1], cc = st[2], d = st[3], e = st[4];
-#pragma unroll
-    for (int r = 0; r < 80; ++r) {
-        if (r >= 16)
-            w[r & 15] = rol32(w[(r + 13) & 15] ^ w[(r + 8) & 15] ^ w[(r + 2) & 15] ^ w[r & 15], 1);
-        const uint32_t f = r < 20 ? ((bb & cc) | (~bb & d))
-                         : r < 40 ? (bb ^ cc ^ d)
-                         : r < 60 ? ((bb & cc) | (bb & d) | (cc & d)) : (bb ^ cc ^ d);
-        const uint32_t k = r < 20 ? 0x5a827999u : r < 40 ? 0x6ed9eba1u : r < 60 ? 0x8f1bbcdcu : 0xca62c1d6u;
-        const uint32_t t = rol32(a, 5) + f + e + k + w[r & 15];
-        e = d; d = cc; cc = rol32(bb, 30); bb = a; a = t;
-    }
-    st[0] += a; st[1] += bb; st[2] += cc; st[3] += d; st[4] += e;
-}
-
-// The GUID's bytes as big-endian words (it follows a 24-byte key at word 6).
-__device__ __forceinline__ uint32_t guid_word(int j)
-{
-    constexpr char g[] = "258EAFA5-E914-47DA-95CA-C5AB0DC85B11";
-    return (uint32_t)(uint8_t)g[4 * j] << 24 | (uint32_t)(uint8_t)g[4 * j + 1] << 16 |
-           (uint32_t)(uint8_t)g[4 * j + 2] << 8 | (uint32_t)(uint8_t)g[4 * j + 3];
-}
-
-// One thread per connection: a connection storm's accept keys at once.
-// A key of 24 bytes (every RFC 6455 client key: base64 of 16 bytes) takes
-// the fast form: its SHA-1 input is 6 key words + 9 GUID words + the 0x80
-// pad in block 0, and a constant block 1 (zeros and the 480-bit length).
-// Any other length builds the message byte by byte.
-#ifndef CFWS_ACCEPT_MIN_BLOCKS
-#define CFWS_ACCEPT_MIN_BLOCKS 1
-#endif
-__global__ void __launch_bounds__(kThreads, CFWS_ACCEPT_MIN_BLOCKS)
-ws_accept_kernel(const uint8_t* __restrict__ keys, const uint64_t* __restrict__ key_off, uint64_t n,
-                 char* __restrict__ out)
-{
-    const uint64_t c = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (c >= n) return;
-    const uint8_t* key = keys + key_off[c];
-    char* o = out + CFWS_WS_ACCEPT_SLOT * c;
-    if (key_off[c + 1] < key_off[c]) {
-        // offsets out of order: no key, an empty slot (a wrapped length would
-        // walk ~2^58 SHA-1 blocks)
-        for (int b = 0; b < CFWS_WS_ACCEPT_SLOT; ++b) o[b] = 0;
-        return;
-    }
-    const uint64_t L = key_off[c + 1] - key_off[c];
-    uint32_t st[5] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u, 0xc3d2e1f0u};
-    if (L == 24) {
-        uint32_t w[16];
-        if ((reinterpret_cast<uintptr_t>(key) & 7u) == 0) {
-            // three 8-byte loads (keys packed 24 bytes apart stay aligned)
-            const uint2* k8 = reinterpret_cast<const uint2*>(key);
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                const uint2 v = k8[t];
-                w[2 * t] = __builtin_bswap32(v.x);
-                w[2 * t + 1] = __builtin_bswap32(v.y);
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < 6; ++t)
-                w[t] = (uint32_t)key[4 * t] << 24 | (uint32_t)key[4 * t + 1] << 16 |
-                       (uint32_t)key[4 * t + 2] << 8 | (uint32_t)key[4 * t + 3];
-        }
-#pragma unroll
-        for (int t = 6; t < 15; ++t) w[t] = guid_word(t - 6);
-        w[15] = 0x80000000u;
-        sha1_block(st, w);
-        uint32_t w2[16];
-#pragma unroll
-        for (int t = 0; t < 15; ++t) w2[t] = 0;
-        w2[15] = 60u * 8u;
-        sha1_block(st, w2);
-    } else {
-        const uint64_t blocks = (L + 36 + 9 + 63) / 64;
-        for (uint64_t b = 0; b < blocks; ++b) {
-            uint32_t w[16];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const uint64_t i = b * 64 + 4 * t;
-                w[t] = accept_msg_byte(key, L, blocks, i) << 24 | accept_msg_byte(key, L, blocks, i + 1) << 16 |
-                       accept_msg_byte(key, L, blocks, i + 2) << 8 | accept_msg_byte(key, L, blocks, i + 3);
-            }
-            sha1_block(st, w);
-        }
-    }
-    // base64 of the 20 hash bytes: 6 full groups + 2 bytes -> 3 chars + '=';
-    // the 32-byte slot written as words: 28 characters, the NUL, 3 zeros
-    uint32_t ow[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int g = 0; g < 7; ++g) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int idx = 3 * g + j;
-            const uint32_t byte = idx < 20 ? (st[idx >> 2] >> (8 * (3 - (idx & 3)))) & 0xffu : 0u;
-            v = v << 8 | byte;
-        }
-        const uint32_t c3 = g < 6 ? b64_char(v & 63) : (uint32_t)'=';
-        ow[g] = b64_char((v >> 18) & 63) | b64_char((v >> 12) & 63) << 8 | b64_char((v >> 6) & 63) << 16 |
-                c3 << 24;
-    }
-    if ((reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
-        uint4* o16 = reinterpret_cast<uint4*>(o);
-        o16[0] = make_uint4(ow[0], ow[1], ow[2], ow[3]);
-        o16[1] = make_uint4(ow[4], ow[5], ow[6], ow[7]);
-    } else {
-#pragma unroll
-        for (int b = 0; b < 29; ++b) o[b] = (char)(ow[b >> 2] >> (8 * (b & 3)));
-    }
-}
-
-// ---------------------------------------------------------------------------
 // receive-buffer frame indexing (co_ws_server.c:107-169)
 // ---------------------------------------------------------------------------
 
@@ -583,19 +438,6 @@ int cfws_index_frames_batch(const void* d_buf, const uint64_t* d_begin, const ui
                                                   d_starts, cap);
     }
     return launch_check("index");
-}
-
-int cfws_ws_accept_keys_batch(const void* d_keys, const uint64_t* d_key_off, size_t n,
-                              char* d_accept, void* stream)
-{
-    const CfwsPassScope pass_scope;
-    if (int rc = check_init()) return rc;
-    if (n == 0) return CFWS_OK;
-    if (!d_keys || !d_key_off || !d_accept)
-        return set_err(CFWS_ERROR_INVALID_ARGUMENT, "accept keys: null pointer", hipSuccess);
-    ws_accept_kernel<<<grid_for(n, kThreads), kThreads, 0, static_cast<hipStream_t>(stream)>>>(
-        static_cast<const uint8_t*>(d_keys), d_key_off, n, d_accept);
-    return launch_check("ws_accept_keys");
 }
 
 void* cfws_mapped_device_pointer(const void* h_ptr)

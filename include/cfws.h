@@ -406,6 +406,64 @@ int cfws_index_frames_batch(const void* d_buf, const uint64_t* d_begin, const ui
 int cfws_ws_accept_keys_batch(const void* d_keys, const uint64_t* d_key_off, size_t n,
                               char* d_accept, void* stream);
 
+/* ---- the rest of the upgrade's key handling (co_ws_http_extension.c) -------
+ * The three calls below allocate nothing, copy nothing from host memory and
+ * do not synchronise: their work is queued on `stream`. None is a timed
+ * pass: a pending cfws_time_next_pass pair is dropped. CFWS_OK, or
+ * CFWS_ERROR_NO_DEVICE / _INVALID_ARGUMENT / _HIP (the device is checked
+ * first, then the arguments; a refused call writes nothing). n == 0 writes
+ * no per-connection output, but still the counters and *d_next_draw when
+ * they are given.
+ *
+ * cfws_ws_client_keys_batch: the Sec-WebSocket-Key values of n_conns
+ * sequential co_http_request_create_ws_upgrade calls (:280-290: co_random of
+ * 16 bytes, co_base64_encode with padding) made after first_draw calls of
+ * random() since srandom(seed). Connection c's nonce byte j is draw
+ * first_draw + 16 c + j of the stream cfws_draw_mask_keys_seeded_at draws
+ * from; its key, 22 characters and "==", goes to d_ws_keys + CFWS_WS_KEY_SLOT
+ * * c as 24 characters, the NUL and 7 zero bytes. d_expect_accept (may be
+ * NULL) gets, per connection, the 32 bytes cfws_ws_accept_keys_batch writes
+ * for that key into an aligned output: the value the server's answer must
+ * carry. *d_next_draw (may be NULL) = first_draw + 16 n_conns: the first_draw
+ * of whatever draws next (cfws_draw_mask_keys_device for the frames those
+ * connections then send). Both outputs 16-byte aligned, 32 n_conns bytes;
+ * first_draw <= 2^62; n_conns < 2^30. One launch, no workspace; the nonces
+ * never go to memory. cfws_ws_client_keys_group_conns: the connections one
+ * workgroup produces (a constant of the build).
+ *
+ * cfws_ws_upgrade_keys_batch: the server's side. Keys as for
+ * cfws_ws_accept_keys_batch (the strlen bytes of each header field). d_valid[c]
+ * = 1 when co_http_request_validate_ws_upgrade accepts the key (:156-170:
+ * co_base64_decode returns true and nonce_length == 16), else 0. The rule is
+ * co_base64.c:94-167's, not RFC 4648's: '\n', '\r' and '=' are skipped
+ * wherever they stand; A-Z a-z 0-9 + / and also ! - : _ and every byte >=
+ * 0x80 are data; any other byte (NUL included) fails; and with L the key's
+ * length the key is valid when nothing failed and floor(3 L / 4) - skipped ==
+ * 16. d_accept (may be NULL) gets what cfws_ws_accept_keys_batch writes, for
+ * every key, valid or not (the response builder hashes whatever the field
+ * holds, :342). A key whose offsets decrease gets d_valid 0 and an all-zero
+ * accept slot. *d_invalid_count (may be NULL; zeroed by the call) = the keys
+ * with d_valid 0.
+ *
+ * cfws_ws_check_accept_batch: the client's check of the answers (:231-254):
+ * d_ok[c] = 1 when strcmp(answer c, expected c) == 0. d_expect_accept holds
+ * 32-byte slots with NUL-terminated strings, as the two calls above and
+ * cfws_ws_accept_keys_batch write them; answer c is the bytes
+ * d_resp[d_resp_off[c], d_resp_off[c + 1]) read as a C string (it ends at
+ * its first NUL or at its end). Decreasing offsets compare unequal.
+ * *d_fail_count (may be NULL; zeroed by the call) = the zeros in d_ok. */
+#define CFWS_WS_KEY_SLOT 32
+int cfws_ws_client_keys_batch(uint32_t seed, uint64_t first_draw, size_t n_conns,
+                              char* d_ws_keys, char* d_expect_accept,
+                              uint64_t* d_next_draw, void* stream);
+size_t cfws_ws_client_keys_group_conns(void);
+int cfws_ws_upgrade_keys_batch(const void* d_keys, const uint64_t* d_key_off, size_t n,
+                               uint8_t* d_valid, char* d_accept,
+                               uint32_t* d_invalid_count, void* stream);
+int cfws_ws_check_accept_batch(const char* d_expect_accept, const void* d_resp,
+                               const uint64_t* d_resp_off, size_t n,
+                               uint8_t* d_ok, uint32_t* d_fail_count, void* stream);
+
 /* ---- WebSocket over HTTP/2 (src/ws_http2) ---------------------------------
  * Send: every WS frame of the batch is serialized (cfws_serialize_batch, into
  * d_wire) and carried in HTTP/2 DATA frames of at most max_frame_size payload
