@@ -7,7 +7,7 @@
 HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_handshake cfws_ops cfws_uniform
+DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_handshake cfws_ops cfws_h2index cfws_uniform
 HOSTSRC  := cfws_frame cfws_pipeline cfws_index cfws_graph
 HDR      := include/cfws.h include/cfws_co_ws_frame.h coldforce_amd/csrc/cfws_internal.h coldforce_amd/csrc/cfws_rules.h coldforce_amd/csrc/cfws_keyrules.h coldforce_amd/csrc/cfws_keydev.h coldforce_amd/csrc/cfws_devpolicy.h
 LIB      := coldforce_amd/libcfws.so
@@ -42,8 +42,22 @@ $(OBJDIR)/%.o: coldforce_amd/csrc/%.cpp $(HDR)
 $(LIB): $(addprefix $(OBJDIR)/,$(addsuffix .o,$(DEVSRC) $(HOSTSRC)))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
+# tools/h2_index_bench.py's host leg (threads of cfws_h2_index_frames calls)
+build/libh2hostwalk.so: tools/h2_index_host_walk.cpp $(LIB) $(HDR)
+	@mkdir -p build
+	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -Iinclude -o $@ $< -Lcoldforce_amd -lcfws \
+	    -Wl,-rpath,'$$ORIGIN/../coldforce_amd' -lpthread
+
 oracle:
 	$(MAKE) -s -C oracle
+
+# the host HTTP/2 walk (cfws_index.cpp alone) in a stand-alone host program
+# under AddressSanitizer + UBSan; tests/test_h2_index.py builds and runs it
+build/h2_index_asan: tests/native/h2_index_asan.cpp coldforce_amd/csrc/cfws_index.cpp $(HDR)
+	@mkdir -p build
+	$(HIPCC) -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Icoldforce_amd/csrc -o $@ \
+	    tests/native/h2_index_asan.cpp coldforce_amd/csrc/cfws_index.cpp
 
 ref: all
 	$(MAKE) -s -C oracle ref

@@ -69,6 +69,8 @@ BATCH_SYMBOLS = (
     "cfws_mapped_device_pointer",
     "cfws_pipeline_set_d2h", "cfws_graph_serialize", "cfws_graph_deserialize", "cfws_graph_launch",
     "cfws_graph_destroy", "cfws_pipeline_h2_serialize", "cfws_pipeline_h2_deserialize",
+    "cfws_h2_index_frames", "cfws_h2_index_workspace_size", "cfws_h2_index_frames_batch",
+    "cfws_pipeline_h2_receive",
 )
 DROPIN_SYMBOLS = (
     "co_ws_frame_serialize", "co_ws_frame_deserialize", "co_ws_frame_create",
@@ -185,6 +187,14 @@ def lib(path: str = LIB_PATH) -> C.CDLL:
         "cfws_index_workspace_size": ([_sz], _sz),
         "cfws_index_frames_batch": ([_vp, _vp, _vp, _sz, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
                                      _sz, _vp], C.c_int),
+        "cfws_h2_index_frames": ([_vp, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _sz, C.POINTER(_u64),
+                                  C.POINTER(C.c_int32)], _sz),
+        "cfws_h2_index_workspace_size": ([_sz], _sz),
+        "cfws_h2_index_frames_batch": ([_vp, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp,
+                                        _vp, _vp, _vp, _sz, _vp], C.c_int),
+        "cfws_pipeline_h2_receive": ([_vp, _vp, _u64, _u64, _u32, _u32, _u64, _u32, _vp, _vp, _vp,
+                                      C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_u64),
+                                      C.POINTER(C.c_int32), _vp, _u64, C.POINTER(_u64)], C.c_int),
         "cfws_ws_accept_keys_batch": ([_vp, _vp, _sz, _vp, _vp], C.c_int),
         "cfws_ws_client_keys_batch": ([_u32, _u64, _sz, _vp, _vp, _vp, _vp], C.c_int),
         "cfws_ws_client_keys_group_conns": ([], _sz),
@@ -907,6 +917,65 @@ def index_frames_batch(buf_t, begin_t, end_t, max_payload: int = DEFAULT_MAX_PAY
     return starts_t, first[:n], consumed[:n], stop[:n], int(total.item())
 
 
+# ---- HTTP/2 receive-buffer frame indexing ------------------------------------
+H2_INDEX_ALL, H2_INDEX_DATA = 0, 1
+
+# cfws_h2_frame_info_t, 16 bytes.
+H2_INFO_DTYPE = np.dtype([("stream_id", "<u4"), ("length", "<u4"), ("advance", "<u4"),
+                          ("type", "u1"), ("flags", "u1"), ("zero", "<u2")])
+assert H2_INFO_DTYPE.itemsize == 16
+
+
+def h2_index_frames(buf: np.ndarray, begin: int = 0, end: int | None = None,
+                    max_frame_size: int = H2_DEFAULT_MAX_FRAME_SIZE, select: int = H2_INDEX_ALL,
+                    stream_id: int = 0, max_starts: int | None = None):
+    """Host walk of one connection's HTTP/2 receive buffer buf[begin, end)
+    (cfws_h2_index_frames): (starts, info, consumed, stop)."""
+    end = buf.size if end is None else end
+    cap = max((end - begin) // 9 + 1, 1) if max_starts is None else max_starts
+    starts = np.zeros(max(cap, 1), dtype=np.uint64)
+    info = np.zeros(max(cap, 1), dtype=H2_INFO_DTYPE)
+    b = buf if buf.size else np.zeros(1, np.uint8)
+    consumed, stop = _u64(0), C.c_int32(0)
+    k = lib().cfws_h2_index_frames(b.ctypes.data, begin, end, max_frame_size, select, stream_id,
+                                   starts.ctypes.data, info.ctypes.data, cap, C.byref(consumed),
+                                   C.byref(stop))
+    return starts[:k], info[:k], int(consumed.value), int(stop.value)
+
+
+def h2_index_frames_batch(buf_t, begin_t, end_t, max_frame_size: int = H2_DEFAULT_MAX_FRAME_SIZE,
+                          select: int = H2_INDEX_ALL, stream_id: int = 0, starts_t=None, info_t=None,
+                          ws_t=None, stream=None, with_info: bool = True):
+    """Device walk of many connections' HTTP/2 receive buffers at once
+    (cfws_h2_index_frames_batch). Returns (starts_t, info_t, first_t,
+    consumed_t, stop_t, total) -- total synchronises. info_t: (capacity, 16)
+    uint8 rows (h2_info_from_device), or None with with_info=False."""
+    import torch
+    n = begin_t.numel()
+    dev = buf_t.device
+    if starts_t is None:
+        span = int((end_t - begin_t).clamp(min=0).sum().item()) if n else 0
+        starts_t = torch.empty(max(span // 9 + n, 1), dtype=torch.int64, device=dev)
+    if info_t is None and with_info:
+        info_t = torch.empty((starts_t.numel(), 16), dtype=torch.uint8, device=dev)
+    first = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    consumed = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    stop = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    if ws_t is None:
+        ws_t = torch.empty(lib().cfws_h2_index_workspace_size(n), dtype=torch.uint8, device=dev)
+    _check(lib().cfws_h2_index_frames_batch(_p(buf_t), _p(begin_t), _p(end_t), n, max_frame_size, select,
+                                            stream_id, _p(starts_t), _p(info_t), starts_t.numel(),
+                                            _p(first), _p(consumed), _p(stop), _p(total), _p(ws_t),
+                                            ws_t.numel(), _stream(stream)),
+           "cfws_h2_index_frames_batch")
+    return starts_t, info_t, first[:n], consumed[:n], stop[:n], int(total.item())
+
+
+def h2_info_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().reshape(-1).view(H2_INFO_DTYPE).copy()
+
+
 # ---- handshake accept keys ---------------------------------------------------
 WS_ACCEPT_SLOT = 32
 
@@ -1087,6 +1156,26 @@ class Pipeline:
                "cfws_pipeline_h2_deserialize")
         m = nm.value
         return h2_status[:n], mdesc[:m], mstatus[:m], tot.value
+
+    def h2_receive(self, h2_ptr: int, begin: int, end: int, payload_ptr: int, payload_capacity: int,
+                   max_frames: int, sid: int = 1, S: int = H2_DEFAULT_MAX_FRAME_SIZE, align: int = 16,
+                   max_payload: int = DEFAULT_MAX_PAYLOAD):
+        """The HTTP/2 receive loop over host bytes [begin, end) for stream
+        sid: index its DATA frames + deserialize (cfws_pipeline_h2_receive).
+        Returns (h2_status, msg_desc, msg_status, consumed, stop, total)."""
+        h2_status = np.zeros(max(max_frames, 1), dtype=np.int32)
+        mdesc = np.zeros(max(max_frames, 1), dtype=DESC_DTYPE)
+        mstatus = np.zeros(max(max_frames, 1), dtype=np.int32)
+        n, nm = C.c_size_t(max_frames), C.c_size_t(0)
+        consumed, stop, tot = C.c_uint64(), C.c_int32(), C.c_uint64()
+        _check(lib().cfws_pipeline_h2_receive(self.h, h2_ptr, begin, end, sid, S, max_payload, align,
+                                              h2_status.ctypes.data, mdesc.ctypes.data,
+                                              mstatus.ctypes.data, C.byref(n), C.byref(nm),
+                                              C.byref(consumed), C.byref(stop), payload_ptr,
+                                              payload_capacity, C.byref(tot)),
+               "cfws_pipeline_h2_receive")
+        m = nm.value
+        return h2_status[:n.value], mdesc[:m], mstatus[:m], consumed.value, stop.value, tot.value
 
     def receive(self, wire_ptr: int, begin: int, end: int, payload_ptr: int, payload_capacity: int,
                 max_frames: int, align: int = 16, max_payload: int = DEFAULT_MAX_PAYLOAD):

@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "cfws.h"
+#include "cfws_rules.h"
 
 namespace {
 
@@ -61,6 +62,42 @@ size_t cfws_index_frames(const void* h_buf, uint64_t begin, uint64_t end, uint64
         if (k == max_starts) { st = CFWS_INDEX_FULL; break; }       // resume at *consumed
         starts[k++] = p;
         p += len;                                                   // co_ws_frame.c:244
+    }
+    if (consumed) *consumed = p;
+    if (stop) *stop = st;
+    return k;
+}
+
+// The HTTP/2 receive loop's walk (co_http2_client.c:462-541) with the hop
+// rule the device walk uses (h2_hop_by, cfws_rules.h). The rule asks for byte
+// i only when i < end - p, so nothing outside [begin, end) is read.
+size_t cfws_h2_index_frames(const void* h_buf, uint64_t begin, uint64_t end, uint32_t max_frame_size,
+                            uint32_t select, uint32_t stream_id, uint64_t* starts,
+                            cfws_h2_frame_info_t* info, size_t max_starts, uint64_t* consumed,
+                            int32_t* stop)
+{
+    const uint8_t* d = static_cast<const uint8_t*>(h_buf);
+    const uint32_t mfs = max_frame_size ? max_frame_size : CFWS_H2_DEFAULT_MAX_FRAME_SIZE;
+    uint64_t p = begin;
+    size_t k = 0;
+    int32_t st = CFWS_H2_PARSE_COMPLETE;
+    if (select > CFWS_H2_INDEX_DATA) {
+        if (consumed) *consumed = begin;
+        if (stop) *stop = CFWS_H2_PARSE_ERROR;
+        return 0;
+    }
+    while (end > p) {                                               // co_http2_client.c:462
+        const uint8_t* f = d + p;
+        const H2Hop h = h2_hop_by([f](uint32_t i) -> uint32_t { return f[i]; }, end - p, mfs);
+        st = h.status;
+        if (st != CFWS_H2_PARSE_COMPLETE) break;                    // :475-536
+        if (h2_selected(h, select, stream_id)) {
+            if (k == max_starts) { st = CFWS_INDEX_FULL; break; }   // resume at *consumed
+            starts[k] = p;
+            if (info) info[k] = cfws_h2_frame_info_t{h.stream_id, h.length, h.advance, h.type, h.flags, 0};
+            ++k;
+        }
+        p += h.advance;                                             // co_http2_frame.c:530
     }
     if (consumed) *consumed = p;
     if (stop) *stop = st;

@@ -5,7 +5,8 @@
 // HTTP/2; cfws_split.hip: the split header / payload ops; cfws_relay.hip: the
 // relay of received frames; cfws_keys.hip: the mask-key draw;
 // cfws_handshake.hip: the upgrade's keys and their checks; cfws_ops.hip:
-// device indexing, copies, fills and the drop-in service).
+// device indexing, copies, fills and the drop-in service; cfws_h2index.hip:
+// HTTP/2 device indexing).
 // Everything here is internal to each unit (anonymous namespace); what the
 // units share is defined once (namespace cfws_rt): the error state and the
 // pass timing in cfws_device.hip; the deserialize plan, the fused
@@ -67,6 +68,13 @@ __global__ void deserialize_plan_apply_kernel(cfws_frame_desc_t* __restrict__ de
                                               uint32_t self_scan, uint64_t* __restrict__ hdr,
                                               uint64_t capacity, uint32_t reassemble, uint32_t* __restrict__ map0,
                                               uint32_t* __restrict__ map1, uint64_t* __restrict__ user_total);
+// The receive-buffer indexers' place pass, defined in cfws_ops.hip (the WS
+// indexer) and launched by cfws_h2index.hip too: thread (c, j) copies
+// connection c's j-th kept start (j < kIndexSlots) to its place, after the
+// scan turned the counts into firsts.
+__global__ void index_place_kernel(const uint64_t* __restrict__ first, const uint64_t* __restrict__ slots,
+                                   const uint64_t* __restrict__ total, uint64_t n, uint64_t* __restrict__ starts,
+                                   uint64_t cap);
 }  // namespace cfws_rt
 
 namespace {
@@ -1920,6 +1928,28 @@ T* ws_ptr(const void* ws, uint64_t off)
 inline bool misaligned(const void* a, const void* b)
 {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) != 0;
+}
+
+// The receive-buffer indexers (cfws_ops.hip: WS; cfws_h2index.hip: HTTP/2)
+// keep each connection's first kIndexSlots starts in workspace slots between
+// the walk and the scan that places them.
+constexpr uint32_t kIndexSlots = 64;
+
+// The index workspace. [0, 64): header; then the scan partials, each
+// connection's kIndexSlots kept starts and its resume position.
+struct IndexLayout {
+    uint64_t partials, slots, resume, bytes;
+};
+
+inline IndexLayout index_layout(uint64_t n)
+{
+    IndexLayout L;
+    uint64_t at = 64;
+    L.partials = at; at = align_up(at + sizeof(uint64_t) * grid_for(n, kScanBlock), 256);
+    L.slots = at; at = align_up(at + sizeof(uint64_t) * kIndexSlots * n, 256);
+    L.resume = at; at = align_up(at + sizeof(uint64_t) * n, 256);
+    L.bytes = at;
+    return L;
 }
 
 inline int zero_totals(const WsLayout& L, void* ws, uint64_t* d_total, hipStream_t st)

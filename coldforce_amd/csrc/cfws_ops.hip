@@ -4,7 +4,28 @@
 // and the synthetic fill. (The split header / payload ops: cfws_split.hip.)
 #include "cfws_kernels.h"
 
+namespace cfws_rt {
+
+// The kept starts to their places: thread (c, j) copies connection c's j-th
+// start (j < kIndexSlots), after the scan turned the counts into firsts.
+__global__ void __launch_bounds__(kThreads)
+index_place_kernel(const uint64_t* __restrict__ first, const uint64_t* __restrict__ slots,
+                   const uint64_t* __restrict__ total, uint64_t n, uint64_t* __restrict__ starts,
+                   uint64_t cap)
+{
+    const uint64_t t = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+    const uint64_t c = t / kIndexSlots, j = t % kIndexSlots;
+    if (c >= n) return;
+    const uint64_t next = c + 1 < n ? first[c + 1] : *total;
+    const uint64_t k = next - first[c];
+    if (j < k && first[c] + j < cap) starts[first[c] + j] = slots[t];
+}
+
+}  // namespace cfws_rt
+
 namespace {
+
+using cfws_rt::index_place_kernel;
 
 // Device -> host copy by a kernel (cfws_copy_to_host): 16-byte stores into
 // device-mapped pinned host memory, any alignment on either side. Running the
@@ -279,8 +300,8 @@ fill_splitmix_kernel(uint8_t* __restrict__ dst, uint64_t n, uint64_t seed, uint6
 // they wait for the scan that places them) and where frame kIndexSlots
 // starts. After the scan, index_place_kernel copies the kept starts to
 // their places, and only connections with more frames than slots walk on
-// from there (index_rest_kernel).
-constexpr uint32_t kIndexSlots = 64;
+// from there (index_rest_kernel). kIndexSlots, the workspace layout and the
+// place pass are shared with the HTTP/2 indexer (cfws_kernels.h).
 
 // One hop of the walk: the header at buf + p of a buffer ending at e, parsed
 // into d (header and payload size: p + both is the next start). The
@@ -324,21 +345,6 @@ index_walk_kernel(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ 
     resume[c] = r;
 }
 
-// The kept starts to their places: thread (c, j) copies connection c's j-th
-// start (j < kIndexSlots), after the scan turned the counts into firsts.
-__global__ void __launch_bounds__(kThreads)
-index_place_kernel(const uint64_t* __restrict__ first, const uint64_t* __restrict__ slots,
-                   const uint64_t* __restrict__ total, uint64_t n, uint64_t* __restrict__ starts,
-                   uint64_t cap)
-{
-    const uint64_t t = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
-    const uint64_t c = t / kIndexSlots, j = t % kIndexSlots;
-    if (c >= n) return;
-    const uint64_t next = c + 1 < n ? first[c + 1] : *total;
-    const uint64_t k = next - first[c];
-    if (j < k && first[c] + j < cap) starts[first[c] + j] = slots[t];
-}
-
 // Connections with more than kIndexSlots frames: the walk on from frame
 // kIndexSlots, writing the rest of their starts in place.
 __global__ void __launch_bounds__(kThreads)
@@ -359,23 +365,6 @@ index_rest_kernel(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ 
         if (k < cap) starts[k] = p;
         p += d.header_size + d.payload_size;
     }
-}
-
-// The index workspace. [0, 64): header; then the scan partials, each
-// connection's kIndexSlots kept starts and its resume position.
-struct IndexLayout {
-    uint64_t partials, slots, resume, bytes;
-};
-
-IndexLayout index_layout(uint64_t n)
-{
-    IndexLayout L;
-    uint64_t at = 64;
-    L.partials = at; at = align_up(at + sizeof(uint64_t) * grid_for(n, kScanBlock), 256);
-    L.slots = at; at = align_up(at + sizeof(uint64_t) * kIndexSlots * n, 256);
-    L.resume = at; at = align_up(at + sizeof(uint64_t) * n, 256);
-    L.bytes = at;
-    return L;
 }
 
 // The grid of a grid-stride kernel over n bytes, a 16-byte chunk per thread

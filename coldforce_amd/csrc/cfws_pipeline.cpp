@@ -796,4 +796,45 @@ int cfws_pipeline_h2_deserialize(cfws_pipeline_t* p, const void* h_h2, uint64_t 
     return CFWS_OK;
 }
 
+// The HTTP/2 receive loop over one connection's host buffer, for one stream:
+// the walk (cfws_h2_index_frames, select = DATA + stream id; co_http2_client.c
+// :462-541) on the calling thread, then cfws_pipeline_h2_deserialize of the
+// DATA frames found, over h_h2[0, *consumed). The plain composition: the walk
+// finishes before the first chunk is staged (cfws_pipeline_receive's walk
+// runs a step ahead of its chunks; this one does not).
+int cfws_pipeline_h2_receive(cfws_pipeline_t* p, const void* h_h2, uint64_t begin, uint64_t end,
+                             uint32_t stream_id, uint32_t max_frame_size, uint64_t max_payload,
+                             uint32_t align, int32_t* h_h2_status, cfws_frame_desc_t* h_msg_desc,
+                             int32_t* h_msg_status, size_t* n_frames, size_t* n_messages,
+                             uint64_t* consumed, int32_t* stop, void* h_payload,
+                             uint64_t payload_capacity, uint64_t* payload_total)
+{
+    const CfwsPassScope pass_scope;
+    (void)cfws_internal_take_pass();   // not timed (cfws_time_next_pass): the pair is dropped
+    if (!p || !n_frames || !n_messages || (end > begin && !h_h2)) return fail("null argument");
+    if (*n_frames && (!h_h2_status || !h_msg_desc || !h_msg_status || !h_payload)) return fail("null argument");
+    if (align == 0 || (align & (align - 1)) || align > 4096) return fail("bad align");
+    // the walk in steps, so the index grows with the frames found and not
+    // with the caller's capacity
+    constexpr size_t kStep = 2048;
+    const size_t cap = *n_frames;
+    std::vector<uint64_t> starts;
+    uint64_t pos = begin;
+    int32_t why = CFWS_H2_PARSE_COMPLETE;
+    for (;;) {
+        const size_t at0 = starts.size(), room = std::min(kStep, cap - at0);
+        starts.resize(at0 + room);
+        const size_t got = cfws_h2_index_frames(h_h2, pos, end, max_frame_size, CFWS_H2_INDEX_DATA, stream_id,
+                                                starts.data() + at0, nullptr, room, &pos, &why);
+        starts.resize(at0 + got);
+        if (why != CFWS_INDEX_FULL || starts.size() == cap) break;
+    }
+    *n_frames = starts.size();
+    if (consumed) *consumed = pos;
+    if (stop) *stop = why;
+    return cfws_pipeline_h2_deserialize(p, h_h2, pos, starts.data(), starts.size(), max_frame_size, max_payload,
+                                        align, h_h2_status, h_msg_desc, h_msg_status, n_messages, h_payload,
+                                        payload_capacity, payload_total);
+}
+
 }  // extern "C"

@@ -68,4 +68,80 @@ __host__ __device__ __forceinline__ H2Frame h2_frame_at(const uint8_t* __restric
     return r;
 }
 
+// One hop of the HTTP/2 receive loop (co_http2_client_on_tcp_receive_ready,
+// co_http2_client.c:462-541, around co_http2_frame_deserialize,
+// co_http2_frame.c:211-533): the frame whose first bytes are b[0..9] (the
+// 9-byte header, then the pad length when there is one), with `avail` bytes
+// left in the buffer (> 0: the loop ends at 0 before any parse), under
+// max_frame. at(i) is byte i; it is asked for byte i only when i < avail and,
+// for byte 9, only when PADDED is set and length >= 1. The decisions keep the
+// reference's order, which decides what wins:
+//   avail < 9 -> MORE_DATA; length > max_frame -> ERROR (:244-247, before the
+//   completeness check); avail - 9 < length -> MORE_DATA (:249-253);
+//   type > 9 -> ERROR (:524-527).
+// Then `need`, the payload bytes the type's fixed fields take (pad length +
+// padding, priority, promised stream id, the fixed-size payloads). Where
+// need > length the reference subtracts past zero in an unsigned length
+// (:281, :316, :331, :445, :483) or reads past the frame into whatever
+// follows and trips its caller's co_assert (co_http2_client.c:471): its
+// behaviour is undefined there. ERROR is THIS LIBRARY'S rule for those frames
+// (as h2_frame_at already decides for DATA), not the reference's.
+// advance is what the parse consumed (`(*index) += data_ptr - data_head`,
+// :530), which is not 9 + length for the fixed-size types: they step over
+// their fields only, and SETTINGS over 6 bytes per parameter of a count cast
+// to uint16_t (:391-392). stream_id keeps the reserved bit (:263-265).
+// Fields other than status are set for a COMPLETE frame only.
+struct H2Hop {
+    int32_t status;
+    uint32_t stream_id, length, advance;
+    uint8_t type, flags;
+};
+
+template <typename At>
+__host__ __device__ __forceinline__ H2Hop h2_hop_by(At at, uint64_t avail, uint32_t max_frame)
+{
+    H2Hop r = {};
+    r.status = CFWS_H2_PARSE_MORE_DATA;
+    if (avail < 9) return r;
+    const uint32_t len = at(0) << 16 | at(1) << 8 | at(2);
+    if (len > max_frame) { r.status = CFWS_H2_PARSE_ERROR; return r; }
+    if (avail - 9 < len) return r;
+    const uint32_t type = at(3), flags = at(4);
+    r.status = CFWS_H2_PARSE_ERROR;
+    if (type > 9) return r;
+    // types with a pad length under PADDED: DATA, HEADERS, PUSH_PROMISE
+    uint32_t need = 0;
+    if ((type == 0 || type == 1 || type == 5) && (flags & 0x8u)) {
+        if (len < 1) return r;
+        need = 1u + at(9);
+    }
+    uint32_t adv = 9u + len;
+    switch (type) {
+    case 1: need += (flags & 0x20u) ? 5u : 0u; break;            // HEADERS + PRIORITY
+    case 2: need = 5; adv = 14; break;                           // PRIORITY
+    case 3: need = 4; adv = 13; break;                           // RST_STREAM
+    case 4: adv = 9u + 6u * ((len / 6u) & 0xffffu); break;       // SETTINGS
+    case 5: need += 4; break;                                    // PUSH_PROMISE
+    case 6: need = 8; adv = 17; break;                           // PING
+    case 7: need = 8; break;                                     // GOAWAY
+    case 8: need = 4; adv = 13; break;                           // WINDOW_UPDATE
+    default: break;                                              // DATA, CONTINUATION
+    }
+    if (need > len) return r;
+    r.status = CFWS_H2_PARSE_COMPLETE;
+    r.stream_id = at(5) << 24 | at(6) << 16 | at(7) << 8 | at(8);
+    r.length = len;
+    r.advance = adv;
+    r.type = (uint8_t)type;
+    r.flags = (uint8_t)flags;
+    return r;
+}
+
+// Is the COMPLETE frame h reported? (select: CFWS_H2_INDEX_ALL / _DATA;
+// stream_id 0: every stream, else the id as read, reserved bit included)
+__host__ __device__ __forceinline__ bool h2_selected(const H2Hop& h, uint32_t select, uint32_t stream_id)
+{
+    return (select == CFWS_H2_INDEX_ALL || h.type == 0) && (stream_id == 0 || h.stream_id == stream_id);
+}
+
 #endif

@@ -515,6 +515,117 @@ int cfws_h2_deserialize_batch(const void* d_h2, uint64_t h2_size, const uint64_t
                               uint64_t* d_payload_total, size_t* n_messages,
                               void* d_workspace, size_t workspace_size, void* stream);
 
+/* ---- HTTP/2 receive-buffer frame indexing ---------------------------------
+ * The frame walk of the reference's HTTP/2 receive loop,
+ * co_http2_client_on_tcp_receive_ready (co_http2_client.c:462-541; the
+ * server's loop is co_http2_server.c:139ff), over one connection's received
+ * bytes buf[begin, end): from the receive index `begin`, while bytes remain,
+ * one co_http2_frame_deserialize (co_http2_frame.c:211-533) per step. A real
+ * receive buffer carries SETTINGS, WINDOW_UPDATE, PING and HEADERS frames and
+ * the frames of other streams (RFC 8441: one WebSocket per stream) between
+ * one stream's DATA frames, and usually ends inside a frame. Each step
+ * decides, in the reference's order:
+ *   1. fewer than 9 bytes left             -> MORE_DATA
+ *   2. length > max_frame_size             -> ERROR (:244-247; before 3)
+ *   3. fewer than 9 + length bytes left    -> MORE_DATA (:249-253)
+ *   4. type > 9                            -> ERROR (:524-527)
+ *   5. need > length                       -> ERROR, where need is the payload
+ *      bytes the type's fixed fields take: DATA PADDED ? 1 + pad : 0; HEADERS
+ *      that + (PRIORITY ? 5 : 0); PRIORITY 5; RST_STREAM 4; SETTINGS 0;
+ *      PUSH_PROMISE (PADDED ? 1 + pad : 0) + 4; PING 8; GOAWAY 8;
+ *      WINDOW_UPDATE 4; CONTINUATION 0. pad is the byte after the header,
+ *      read only when PADDED is set and length >= 1 (PADDED with length 0 ->
+ *      ERROR). The reference's behaviour is UNDEFINED for these frames (it
+ *      underflows an unsigned length, :281 :316 :331 :445 :483, or reads past
+ *      the frame and trips co_assert, co_http2_client.c:471): ERROR is this
+ *      library's rule, as for padded DATA in cfws_h2_deserialize_batch.
+ *   6. COMPLETE; the receive index moves by what the parse consumed (:530),
+ *      not by 9 + length: DATA, HEADERS, PUSH_PROMISE, GOAWAY, CONTINUATION
+ *      9 + length; PRIORITY 14; RST_STREAM, WINDOW_UPDATE 13; PING 17;
+ *      SETTINGS 9 + 6 * ((length / 6) mod 65536) (the parameter count is a
+ *      uint16_t, :391-392). A control frame whose length differs from its
+ *      fixed size therefore leaves the next parse inside it, as in the
+ *      reference.
+ * The stream id is the header's 4 bytes as the reference reads them: the
+ * reserved bit is kept (:263-265; co_http2_get_stream looks that value up).
+ * max_frame_size 0 = 16384. A frame is selected when (select ==
+ * CFWS_H2_INDEX_ALL or its type is 0) and (stream_id == 0 or its stream id as
+ * read == stream_id). The walk passes over every COMPLETE frame; only
+ * selected frames are reported: starts[k], and info[k] when info is not
+ * NULL. *consumed is where the reference leaves receive_data.index; *stop:
+ *   CFWS_H2_PARSE_COMPLETE   every byte consumed (also begin >= end: no
+ *                            frames, consumed = begin)
+ *   CFWS_H2_PARSE_MORE_DATA  the frame at *consumed is incomplete: wait
+ *   CFWS_H2_PARSE_ERROR      the frame at *consumed; the reference closes
+ *                            the connection with FRAME_SIZE_ERROR
+ *                            (co_http2_client.c:526-536)
+ *   CFWS_INDEX_FULL          host form only: `starts` is full and another
+ *                            SELECTED frame follows, at *consumed (unselected
+ *                            frames before it are consumed); resuming from
+ *                            *consumed continues the same walk.
+ * No byte outside [begin, end) is read. The server's 24-byte connection
+ * preface (co_http2_server.c:32-50) is the caller's to skip through `begin`.
+ * select above 1: the host form returns 0 starts, stop CFWS_H2_PARSE_ERROR
+ * and consumed = begin; the device form CFWS_ERROR_INVALID_ARGUMENT.
+ *
+ * Host form: one connection, on the calling thread. Returns the number of
+ * starts written. */
+#define CFWS_H2_INDEX_ALL   0u   /* every COMPLETE frame */
+#define CFWS_H2_INDEX_DATA  1u   /* type 0 only */
+
+typedef struct cfws_h2_frame_info {   /* 16 bytes */
+    uint32_t stream_id;   /* the 4 bytes as the reference reads them: reserved bit kept */
+    uint32_t length;      /* the header's 24-bit length */
+    uint32_t advance;     /* what the receive index moves by (rule 6) */
+    uint8_t  type, flags;
+    uint16_t zero;
+} cfws_h2_frame_info_t;
+
+size_t cfws_h2_index_frames(const void* h_buf, uint64_t begin, uint64_t end,
+                            uint32_t max_frame_size, uint32_t select, uint32_t stream_id,
+                            uint64_t* starts, cfws_h2_frame_info_t* info, size_t max_starts,
+                            uint64_t* consumed, int32_t* stop);
+
+/* Device form: n_conns connections of one device arena at once, connection
+ * c = d_buf[d_begin[c], d_end[c]), as cfws_index_frames_batch: d_first[c] =
+ * index of c's first selected start in d_starts (exclusive prefix sum of the
+ * per-connection selected counts), *d_total = all selected frames
+ * (unclamped); positions >= starts_capacity are not written, in d_starts and
+ * d_info alike. d_info may be NULL; otherwise it must be 16-byte aligned
+ * (each record is one 16-byte store). d_consumed / d_stop per connection as
+ * above. Nothing is allocated and nothing synchronises; not a timed pass (a
+ * pending cfws_time_next_pass pair is dropped). Errors, device check first:
+ * null pointers (as cfws_index_frames_batch), select > 1 or a misaligned
+ * d_info -> CFWS_ERROR_INVALID_ARGUMENT; workspace too small ->
+ * CFWS_ERROR_WORKSPACE; nothing is written. n_conns == 0 writes *d_total = 0
+ * only. The workspace (cfws_h2_index_workspace_size) is the WS indexer's: 64
+ * starts per connection between the walk and the scan that places them, 520
+ * bytes per connection; the records of those 64 are re-derived from the 9
+ * header bytes at each kept start, so they cost no workspace.
+ * What the output feeds: with select = CFWS_H2_INDEX_DATA and a stream id,
+ * d_starts is exactly the "one stream, in order" index
+ * cfws_h2_deserialize_batch takes (the other frames still lie in the buffer
+ * between the indexed ones, which that call allows). That receive pools
+ * until END_STREAM across its whole index, so the starts of several
+ * connections go into one call only when each connection's selected frames
+ * end with END_STREAM (the last d_info.flags of each connection shows
+ * whether they do); otherwise make one call per connection, using d_first.
+ * Speed (profiles/h2index/h2_index_bench.jsonl): a
+ * tick of 16,384 connections x 64 KiB indexes in about 0.11 ms at 62 DATA
+ * frames of 1,041 bytes per connection (9.6 G frames/s; 0.08 ms with d_info
+ * NULL, the WS indexer's time for the same frames) and 0.03 ms at 3 frames
+ * of 16,393 bytes; cfws_h2_index_frames over the same bytes in host memory
+ * on 16 threads took 2.1-2.2 and 0.5-0.6 ms, so the device form is the faster
+ * one at both shapes when the buffers are already in device memory. */
+size_t cfws_h2_index_workspace_size(size_t n_conns);
+int cfws_h2_index_frames_batch(const void* d_buf, const uint64_t* d_begin, const uint64_t* d_end,
+                               size_t n_conns, uint32_t max_frame_size, uint32_t select,
+                               uint32_t stream_id, uint64_t* d_starts,
+                               cfws_h2_frame_info_t* d_info, uint64_t starts_capacity,
+                               uint64_t* d_first, uint64_t* d_consumed, int32_t* d_stop,
+                               uint64_t* d_total, void* d_workspace, size_t workspace_size,
+                               void* stream);
+
 /* ---- host-memory pipeline ------------------------------------------------
  * The same codec over HOST buffers (socket send/receive side): the batch is
  * cut into chunks of frames; `depth` slots (1..4), each with a stream and
@@ -569,6 +680,25 @@ int cfws_pipeline_h2_deserialize(cfws_pipeline_t* pipeline, const void* h_h2, ui
                                  cfws_frame_desc_t* h_msg_desc, int32_t* h_msg_status,
                                  size_t* n_messages, void* h_payload, uint64_t payload_capacity,
                                  uint64_t* payload_total);
+/* The HTTP/2 receive loop over one connection's host buffer h_h2[begin, end)
+ * for one stream: cfws_h2_index_frames(select = CFWS_H2_INDEX_DATA,
+ * stream_id) on the calling thread, then cfws_pipeline_h2_deserialize of the
+ * DATA frames it found with h2_size = *consumed (bytes past the walk's stop
+ * are never staged). The plain composition: the walk finishes before the
+ * first chunk is staged (it is not interleaved with the chunks as
+ * cfws_pipeline_receive's is). *n_frames: in, the capacity of h_h2_status /
+ * h_msg_desc / h_msg_status; out, the DATA frames indexed. *consumed / *stop
+ * as cfws_h2_index_frames reports them (CFWS_INDEX_FULL: another DATA frame
+ * of the stream follows at *consumed; call again from there; each call
+ * pools its own DATA frames only, as cfws_pipeline_h2_deserialize does, so
+ * size the capacity to end where messages do). */
+int cfws_pipeline_h2_receive(cfws_pipeline_t* pipeline, const void* h_h2, uint64_t begin,
+                             uint64_t end, uint32_t stream_id, uint32_t max_frame_size,
+                             uint64_t max_payload, uint32_t align, int32_t* h_h2_status,
+                             cfws_frame_desc_t* h_msg_desc, int32_t* h_msg_status,
+                             size_t* n_frames, size_t* n_messages, uint64_t* consumed,
+                             int32_t* stop, void* h_payload, uint64_t payload_capacity,
+                             uint64_t* payload_total);
 
 /* How the pipeline's D2H leg moves bytes into a MAPPED host output arena
  * (hipHostMalloc(..., hipHostMallocMapped)); unmapped arenas always take
