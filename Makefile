@@ -9,7 +9,7 @@ ARCH     ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_handshake cfws_ops cfws_h2index cfws_uniform
 HOSTSRC  := cfws_frame cfws_pipeline cfws_index cfws_graph
-HDR      := include/cfws.h include/cfws_co_ws_frame.h coldforce_amd/csrc/cfws_internal.h coldforce_amd/csrc/cfws_rules.h coldforce_amd/csrc/cfws_keyrules.h coldforce_amd/csrc/cfws_keydev.h coldforce_amd/csrc/cfws_devpolicy.h
+HDR      := include/cfws.h include/cfws_co_ws_frame.h coldforce_amd/csrc/cfws_internal.h coldforce_amd/csrc/cfws_rules.h coldforce_amd/csrc/cfws_chunks.h coldforce_amd/csrc/cfws_keyrules.h coldforce_amd/csrc/cfws_keydev.h coldforce_amd/csrc/cfws_devpolicy.h
 LIB      := coldforce_amd/libcfws.so
 OBJDIR   := build
 
@@ -58,6 +58,15 @@ build/h2_index_asan: tests/native/h2_index_asan.cpp coldforce_amd/csrc/cfws_inde
 	$(HIPCC) -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Icoldforce_amd/csrc -o $@ \
 	    tests/native/h2_index_asan.cpp coldforce_amd/csrc/cfws_index.cpp
+
+# the pipeline's chunk cuts (cfws_chunks.h, header only) in a stand-alone host
+# program under AddressSanitizer + UBSan; tests/test_pipeline_chunks.py builds
+# and runs it
+build/chunks_test: tests/native/chunks_test.cpp $(HDR)
+	@mkdir -p build
+	$(HIPCC) -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Icoldforce_amd/csrc -o $@ \
+	    tests/native/chunks_test.cpp
 
 ref: all
 	$(MAKE) -s -C oracle ref

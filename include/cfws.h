@@ -631,7 +631,9 @@ int cfws_h2_index_frames_batch(const void* d_buf, const uint64_t* d_begin, const
  * cut into chunks of frames; `depth` slots (1..4), each with a stream and
  * device staging of chunk_bytes per direction, overlap H2D, the device plan +
  * kernels and D2H of consecutive chunks. Host buffers should be pinned.
- * Synchronous: results are in host memory on return.
+ * Synchronous: results are in host memory on return. On an error return no
+ * copy is in flight either (the caller's buffers may be freed or reused), the
+ * outputs' contents are unspecified, and the pipeline may be used again.
  * max_frames bounds the frames per chunk (descriptor staging). */
 typedef struct cfws_pipeline cfws_pipeline_t;
 int cfws_pipeline_create(uint64_t chunk_bytes, size_t max_frames, int depth,

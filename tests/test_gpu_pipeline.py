@@ -279,3 +279,155 @@ def test_pipeline_h2_deserialize_matches_oracle(chunk, depth, S, align):
             assert np.array_equal(md[f], e["msg_desc"][f]), (cap, f)
         assert np.array_equal(out[:tot], e["payload"][:tot]), cap
     pl.close()
+
+
+def _frames_then_big(rng, n_small, big):
+    """n_small frames of at most 1,000 bytes, then one of `big` bytes (none
+    for big = 0), over a 64 KiB payload arena."""
+    sizes = [rng.choice([0, 1, 125, 126, 500, 1000]) for _ in range(n_small)] + ([big] if big else [])
+    d = np.zeros(len(sizes), dtype=cfws.DESC_DTYPE)
+    for i, sz in enumerate(sizes):
+        d[i] = (rng.randrange(0, (1 << 16) - sz), 0, sz, rng.getrandbits(32), 1, rng.choice([1, 2, 9]),
+                rng.random() < .7, 0)
+    return d
+
+
+DESC_FIELDS = ("payload_off", "wire_off", "payload_size", "mask_key", "fin", "opcode", "mask", "header_size")
+
+
+def _pipeline_case(pl, kind, d, payload_t, payload):
+    """One call of `kind` on pipeline pl over the frames d, prepared: returns
+    (output arena, run). run() makes the call (which may raise CodecError) and
+    asserts that its results equal the oracle's exactly."""
+    S = 1000
+    if kind == "serialize":
+        exp, exp_d = O.serialize_batch(payload, d.view(O.DESC_DTYPE))
+        out_t, out = pinned(len(exp) + 64)
+
+        def run():
+            tot = pl.serialize(payload_t.data_ptr(), d, out_t.data_ptr(), out.size)
+            assert tot == len(exp) and np.array_equal(d["wire_off"], exp_d["wire_off"])
+            assert np.array_equal(out[:tot], exp)
+    elif kind == "h2_serialize":
+        exp, exp_d = O.h2_serialize_batch(payload, d.copy(), 5, S)
+        out_t, out = pinned(len(exp) + 64)
+
+        def run():
+            tot = pl.h2_serialize(payload_t.data_ptr(), d, out_t.data_ptr(), out.size, 5, S)
+            assert tot == len(exp) and np.array_equal(d["header_size"], exp_d["header_size"])
+            assert np.array_equal(out[:tot], exp)
+    elif kind == "deserialize":
+        raw, _ = O.serialize_batch(payload, d.view(O.DESC_DTYPE))
+        wire_t, wire = pinned(len(raw))
+        wire[:len(raw)] = raw
+        starts, _ = O.index_frames(wire[:len(raw)], len(d) + 1)
+        assert len(starts) == len(d)
+        cap = len(raw) + 16 * len(starts) + 64
+        out_t, out = pinned(cap)
+
+        def run():
+            desc, st, tot = pl.deserialize(wire_t.data_ptr(), len(raw), starts, out_t.data_ptr(), cap)
+            e_out, e_d, e_st, e_tot = O.deserialize_batch(wire[:len(raw)], starts, align=16, capacity=cap)
+            assert tot == e_tot and np.array_equal(st, e_st)
+            for f in DESC_FIELDS:
+                assert np.array_equal(desc[f], e_d[f]), f
+            assert np.array_equal(out[:tot], e_out[:tot])
+    else:
+        h2, _ = O.h2_serialize_batch(payload, d, 1, S)
+        index = O.h2_index(h2)
+        h2_t, h2_np = pinned(len(h2))
+        h2_np[:len(h2)] = h2
+        cap = len(h2) + 16 * len(index) + 64
+        out_t, out = pinned(cap)
+
+        def run():
+            st, md, ms, tot = pl.h2_deserialize(h2_t.data_ptr(), len(h2), index, out_t.data_ptr(), cap, S=S)
+            e = O.h2_deserialize_batch(h2, index, S, O.DEFAULT_MAX_PAYLOAD, 16, None, cap)
+            assert np.array_equal(st, e["h2_status"])
+            assert len(md) == e["n_msg"] and tot == e["total"] and np.array_equal(ms, e["msg_status"])
+            for f in DESC_FIELDS:
+                assert np.array_equal(md[f], e["msg_desc"][f]), f
+            assert np.array_equal(out[:tot], e["payload"][:tot])
+    return out, run
+
+
+@pytest.mark.parametrize("depth", [3, 1])
+@pytest.mark.parametrize("kind", ["serialize", "h2_serialize", "deserialize", "h2_deserialize"])
+def test_pipeline_error_return_is_drained_and_pipeline_reusable(kind, depth):
+    """An error return from inside the chunk loop (here: after about 40 good
+    frames, a 9,000-byte frame -- for h2_deserialize a message of ten DATA
+    frames -- that a chunk of 8,192 bytes / 8 frames cannot hold) leaves no
+    copy in flight: the output arena does not change after the call returned.
+    The same pipeline then runs a valid batch with the oracle's results. (An
+    undrained build can pass the first half by luck; a drained one cannot fail
+    it.)"""
+    rng = random.Random(depth * 7 + len(kind))
+    payload_t, payload = pinned(1 << 16)
+    payload[:] = O.fill_splitmix(payload.size, 41, 0)
+    pl = make_pipeline(chunk_bytes=8192, max_frames=8, depth=depth)
+    try:
+        out, run = _pipeline_case(pl, kind, _frames_then_big(rng, 40, 9000), payload_t, payload)
+        with pytest.raises(cfws.CodecError):
+            run()
+        after = out.copy()
+        torch.cuda.synchronize()
+        assert np.array_equal(out, after)
+        out, run = _pipeline_case(pl, kind, _frames_then_big(rng, 60, 0), payload_t, payload)
+        run()
+    finally:
+        pl.close()
+
+
+@pytest.mark.parametrize("which", ["below", "step", "equal", "above"])
+def test_pipeline_h2_receive_walk_in_steps(which):
+    """cfws_pipeline_h2_receive walks through the same stepped walk as
+    cfws_pipeline_receive (steps of 2,048 starts): over a connection buffer
+    with more DATA frames of the stream than one step, between frames of
+    another stream and control frames, its end equals one
+    cfws_h2_index_frames call over the whole buffer at every frame limit
+    (CFWS_INDEX_FULL only when another DATA frame of the stream follows), and
+    the statuses, messages and payloads equal the oracle's over that index."""
+    import h2_index_util as U
+    rng = random.Random(2100)
+    sizes = [rng.choice([0, 1, 5, 26, 27, 60, 126, 200]) for _ in range(730)]
+    d = np.zeros(len(sizes), dtype=cfws.DESC_DTYPE)
+    off = 0
+    for i, sz in enumerate(sizes):
+        d[i] = (off, 0, sz, rng.getrandbits(32), 1, 2, 1, 0)
+        off += sz
+    mine, _ = O.h2_serialize_batch(O.fill_splitmix(off + 16, 9, 0), d, 1, 30)     # DATA frames of 0-30 bytes
+    cuts = [int(x) for x in O.h2_index(mine)] + [len(mine)]
+    others = [lambda: U.frame(U.T_SETTINGS, 0, 0, rng.randbytes(12)),
+              lambda: U.frame(U.T_PING, rng.randrange(2), 0, rng.randbytes(8)),
+              lambda: U.frame(U.T_WINUP, 0, 3, rng.randbytes(4)),
+              lambda: U.frame(U.T_DATA, rng.randrange(2), 3, rng.randbytes(rng.randrange(31)))]
+    parts = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        parts.append(mine[a:b].tobytes())
+        if rng.random() < .4:
+            parts.append(rng.choice(others)())
+    blob = b"".join(parts)
+    buf = np.frombuffer(blob, np.uint8)
+    count = len(cuts) - 1
+    assert 2100 <= count <= 2400
+    max_frames = {"below": count - 37, "step": 2048, "equal": count, "above": count + 500}[which]
+    es, _, e_con, e_stop = cfws.h2_index_frames(buf, 0, len(blob), 16384, U.DATA_ONLY, 1,
+                                                max_starts=max_frames)
+    assert e_stop == (U.INDEX_FULL if max_frames < count else U.COMPLETE) and len(es) == min(max_frames, count)
+    h2_t, h2_np = pinned(len(blob))
+    h2_np[:len(blob)] = buf
+    cap = len(blob) + 16 * count + 64
+    out_t, out = pinned(cap)
+    e = O.h2_deserialize_batch(buf[:e_con], es, 16384, O.DEFAULT_MAX_PAYLOAD, 16, None, cap)
+    pl = make_pipeline(chunk_bytes=1 << 16, max_frames=700, depth=3)
+    try:
+        st, md, ms, consumed, stop, tot = pl.h2_receive(h2_t.data_ptr(), 0, len(blob), out_t.data_ptr(), cap,
+                                                        max_frames=max_frames, sid=1)
+    finally:
+        pl.close()
+    assert (consumed, stop) == (e_con, e_stop)
+    assert len(st) == len(es) and np.array_equal(st, e["h2_status"])
+    assert len(md) == e["n_msg"] and tot == e["total"] and np.array_equal(ms, e["msg_status"])
+    for f in DESC_FIELDS:
+        assert np.array_equal(md[f], e["msg_desc"][f]), f
+    assert np.array_equal(out[:tot], e["payload"][:tot])
