@@ -844,24 +844,29 @@ def h2_serialize(payload_t, desc_t, wire_t, h2_t, sid: int = 1, S: int = H2_DEFA
 
 def h2_deserialize(h2_t, h2_size: int, index_t, pool_t, payload_t, S: int = H2_DEFAULT_MAX_FRAME_SIZE,
                    max_payload: int = DEFAULT_MAX_PAYLOAD, align: int = 16, ws_t=None, stream=None,
-                   all_rows: bool = False):
+                   all_rows: bool = False, h2_status_t=None, msg_desc_t=None, msg_status_t=None,
+                   total_t=None, n_messages_init: int = 0):
     """HTTP/2 DATA frames at index_t -> pooled WS messages -> payloads.
     Returns (h2_status_t, msg_desc_t, msg_status_t, total_t, n_messages).
     n_messages is final on return; the tensors are written by work still
     queued on `stream` (synchronise it before reading them on another).
     all_rows: return every message row (one per DATA frame; rows past
-    n_messages are empty entries) instead of the first n_messages."""
+    n_messages are empty entries) instead of the first n_messages.
+    h2_status_t, msg_desc_t, msg_status_t, total_t: the caller's output
+    tensors (allocated when not given); n_messages_init: what the host count
+    word holds before the call."""
     import torch
     n = index_t.numel()
     dev = h2_t.device
-    h2_status = torch.empty(n, dtype=torch.int32, device=dev)
-    msg_desc = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
-    msg_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    total = torch.empty(1, dtype=torch.int64, device=dev)      # always written by the library
+    h2_status = torch.empty(n, dtype=torch.int32, device=dev) if h2_status_t is None else h2_status_t
+    msg_desc = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev) if msg_desc_t is None else msg_desc_t
+    msg_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if msg_status_t is None else msg_status_t
+    # always written by the library
+    total = torch.empty(1, dtype=torch.int64, device=dev) if total_t is None else total_t
     if ws_t is None:
         ws_t = torch.empty(lib().cfws_h2_deserialize_workspace_size(n, pool_t.numel(), payload_t.numel()),
                            dtype=torch.uint8, device=dev)
-    n_msg = C.c_size_t(0)
+    n_msg = C.c_size_t(n_messages_init)
     _check(lib().cfws_h2_deserialize_batch(_p(h2_t), h2_size, _p(index_t), n, S, _p(h2_status),
                                            _p(pool_t), pool_t.numel(), max_payload, align,
                                            _p(msg_desc), _p(msg_status), _p(payload_t),
@@ -893,20 +898,22 @@ def index_frames(buf: np.ndarray, begin: int = 0, end: int | None = None,
 
 
 def index_frames_batch(buf_t, begin_t, end_t, max_payload: int = DEFAULT_MAX_PAYLOAD,
-                       starts_t=None, ws_t=None, stream=None):
+                       starts_t=None, ws_t=None, stream=None, first_t=None, consumed_t=None, stop_t=None,
+                       total_t=None):
     """Device receive-loop walk of many connections at once
     (cfws_index_frames_batch). Returns (starts_t, first_t, consumed_t,
-    stop_t, total) -- total synchronises."""
+    stop_t, total) -- total synchronises. first_t, consumed_t, stop_t
+    (max(n, 1) entries) and total_t are allocated when not given."""
     import torch
     n = begin_t.numel()
     dev = buf_t.device
     if starts_t is None:
         span = int((end_t - begin_t).clamp(min=0).sum().item()) if n else 0
         starts_t = torch.empty(max(span // 2 + n, 1), dtype=torch.int64, device=dev)
-    first = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    consumed = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    stop = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    first = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if first_t is None else first_t
+    consumed = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if consumed_t is None else consumed_t
+    stop = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if stop_t is None else stop_t
+    total = torch.zeros(1, dtype=torch.int64, device=dev) if total_t is None else total_t
     if ws_t is None:
         ws_t = torch.empty(lib().cfws_index_workspace_size(n), dtype=torch.uint8, device=dev)
     _check(lib().cfws_index_frames_batch(_p(buf_t), _p(begin_t), _p(end_t), n, max_payload,
@@ -945,11 +952,14 @@ def h2_index_frames(buf: np.ndarray, begin: int = 0, end: int | None = None,
 
 def h2_index_frames_batch(buf_t, begin_t, end_t, max_frame_size: int = H2_DEFAULT_MAX_FRAME_SIZE,
                           select: int = H2_INDEX_ALL, stream_id: int = 0, starts_t=None, info_t=None,
-                          ws_t=None, stream=None, with_info: bool = True):
+                          ws_t=None, stream=None, with_info: bool = True, first_t=None, consumed_t=None,
+                          stop_t=None, total_t=None):
     """Device walk of many connections' HTTP/2 receive buffers at once
     (cfws_h2_index_frames_batch). Returns (starts_t, info_t, first_t,
     consumed_t, stop_t, total) -- total synchronises. info_t: (capacity, 16)
-    uint8 rows (h2_info_from_device), or None with with_info=False."""
+    uint8 rows (h2_info_from_device), or None with with_info=False. first_t,
+    consumed_t, stop_t (max(n, 1) entries) and total_t are allocated when
+    not given."""
     import torch
     n = begin_t.numel()
     dev = buf_t.device
@@ -958,10 +968,10 @@ def h2_index_frames_batch(buf_t, begin_t, end_t, max_frame_size: int = H2_DEFAUL
         starts_t = torch.empty(max(span // 9 + n, 1), dtype=torch.int64, device=dev)
     if info_t is None and with_info:
         info_t = torch.empty((starts_t.numel(), 16), dtype=torch.uint8, device=dev)
-    first = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    consumed = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    stop = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    first = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if first_t is None else first_t
+    consumed = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if consumed_t is None else consumed_t
+    stop = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if stop_t is None else stop_t
+    total = torch.zeros(1, dtype=torch.int64, device=dev) if total_t is None else total_t
     if ws_t is None:
         ws_t = torch.empty(lib().cfws_h2_index_workspace_size(n), dtype=torch.uint8, device=dev)
     _check(lib().cfws_h2_index_frames_batch(_p(buf_t), _p(begin_t), _p(end_t), n, max_frame_size, select,
