@@ -71,6 +71,8 @@ BATCH_SYMBOLS = (
     "cfws_graph_destroy", "cfws_pipeline_h2_serialize", "cfws_pipeline_h2_deserialize",
     "cfws_h2_index_frames", "cfws_h2_index_workspace_size", "cfws_h2_index_frames_batch",
     "cfws_pipeline_h2_receive",
+    "cfws_messages_from_frames", "cfws_messages_workspace_size", "cfws_messages_group_frames",
+    "cfws_messages_batch",
 )
 DROPIN_SYMBOLS = (
     "co_ws_frame_serialize", "co_ws_frame_deserialize", "co_ws_frame_create",
@@ -192,6 +194,11 @@ def lib(path: str = LIB_PATH) -> C.CDLL:
         "cfws_h2_index_workspace_size": ([_sz], _sz),
         "cfws_h2_index_frames_batch": ([_vp, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp,
                                         _vp, _vp, _vp, _sz, _vp], C.c_int),
+        "cfws_messages_from_frames": ([_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, C.POINTER(_u64)], _sz),
+        "cfws_messages_workspace_size": ([_sz, _sz], _sz),
+        "cfws_messages_group_frames": ([], _sz),
+        "cfws_messages_batch": ([_vp, _vp, _sz, _vp, _sz, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _sz, _vp],
+                                C.c_int),
         "cfws_pipeline_h2_receive": ([_vp, _vp, _u64, _u64, _u32, _u32, _u64, _u32, _vp, _vp, _vp,
                                       C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_u64),
                                       C.POINTER(C.c_int32), _vp, _u64, C.POINTER(_u64)], C.c_int),
@@ -984,6 +991,87 @@ def h2_index_frames_batch(buf_t, begin_t, end_t, max_frame_size: int = H2_DEFAUL
 
 def h2_info_from_device(t) -> np.ndarray:
     return t.cpu().numpy().reshape(-1).view(H2_INFO_DTYPE).copy()
+
+
+# ---- message and control tables of received frames ---------------------------
+MESSAGE_FINAL, MESSAGE_CUT, MESSAGE_OPEN, MESSAGE_HEADLESS, MESSAGE_LOST_BYTES = 1, 2, 4, 8, 16
+
+# cfws_message_t, 32 bytes.
+MESSAGE_DTYPE = np.dtype([("payload_off", "<u8"), ("payload_size", "<u8"), ("first_frame", "<u4"),
+                          ("n_fragments", "<u4"), ("conn", "<u4"), ("opcode", "u1"), ("flags", "u1"),
+                          ("zero", "<u2")])
+assert MESSAGE_DTYPE.itemsize == 32
+
+
+def messages_from_frames(desc: np.ndarray, status: np.ndarray | None = None, conn_first: np.ndarray | None = None,
+                         msg_capacity: int | None = None, control_capacity: int | None = None):
+    """Host message walk (cfws_messages_from_frames): (msgs, conn_first_msg,
+    control, n_messages, n_control). msgs and control hold min(total,
+    capacity) rows (the capacities default to the frame count); the totals
+    are unclamped. conn_first_msg is None without conn_first."""
+    d = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+    n = d.size
+    st = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+    cf = None if conn_first is None else np.ascontiguousarray(conn_first, dtype=np.uint64)
+    mcap = n if msg_capacity is None else msg_capacity
+    ccap = n if control_capacity is None else control_capacity
+    msgs = np.zeros(max(mcap, 1), dtype=MESSAGE_DTYPE)
+    control = np.zeros(max(ccap, 1), dtype=np.uint32)
+    cfm = None if cf is None else np.zeros(max(cf.size, 1), dtype=np.uint64)
+    n_control = _u64(0)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    m = lib().cfws_messages_from_frames(ptr(d), ptr(st), n, ptr(cf), 0 if cf is None else cf.size, ptr(msgs),
+                                        mcap, ptr(cfm), ptr(control), ccap, C.byref(n_control))
+    nc = int(n_control.value)
+    return (msgs[:min(m, mcap)], None if cf is None else cfm[:cf.size], control[:min(nc, ccap)], int(m), nc)
+
+
+def messages_group_frames() -> int:
+    """Frames one workgroup of cfws_messages_batch takes (for tests that
+    place messages across its boundaries)."""
+    return int(lib().cfws_messages_group_frames())
+
+
+def messages_workspace(n_frames: int, n_conns: int = 0, device="cuda"):
+    import torch
+    return torch.empty(lib().cfws_messages_workspace_size(n_frames, n_conns), dtype=torch.uint8, device=device)
+
+
+def messages_batch(desc_t, status_t=None, conn_first_t=None, msgs_t=None, control_t=None, ws_t=None,
+                   stream=None, conn_first_msg_t=None, n_messages_t=None, n_control_t=None):
+    """Message and control tables of device-resident frames
+    (cfws_messages_batch). desc_t: (n, 32) uint8 rows; status_t: int32 or
+    None (every frame COMPLETE); conn_first_t: int64 first frame of each
+    connection (index_frames_batch's first_t) or None for one connection.
+    Returns (msgs_t, conn_first_msg_t, control_t, n_messages, n_control) --
+    the totals synchronise. msgs_t: (capacity, 32) uint8 rows
+    (messages_from_device); control_t: int32 frame indices. msgs_t and
+    control_t (n rows each), conn_first_msg_t, the total tensors and the
+    workspace are allocated when not given."""
+    import torch
+    n = desc_t.shape[0]
+    dev = desc_t.device
+    n_conns = 0 if conn_first_t is None else conn_first_t.numel()
+    if msgs_t is None:
+        msgs_t = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
+    if control_t is None:
+        control_t = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    if conn_first_msg_t is None and conn_first_t is not None:
+        conn_first_msg_t = torch.empty(max(n_conns, 1), dtype=torch.int64, device=dev)
+    n_msg = torch.zeros(1, dtype=torch.int64, device=dev) if n_messages_t is None else n_messages_t
+    n_ctl = torch.zeros(1, dtype=torch.int64, device=dev) if n_control_t is None else n_control_t
+    if ws_t is None:
+        ws_t = messages_workspace(n, n_conns, dev)
+    _check(lib().cfws_messages_batch(_p(desc_t), _p(status_t), n, _p(conn_first_t), n_conns, _p(msgs_t),
+                                     msgs_t.shape[0], _p(conn_first_msg_t), _p(n_msg), _p(control_t),
+                                     control_t.numel(), _p(n_ctl), _p(ws_t), ws_t.numel(), _stream(stream)),
+           "cfws_messages_batch")
+    cfm = None if conn_first_msg_t is None else conn_first_msg_t[:max(n_conns, 1) if conn_first_t is None else n_conns]
+    return msgs_t, cfm, control_t, int(n_msg.item()), int(n_ctl.item())
+
+
+def messages_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().reshape(-1).view(MESSAGE_DTYPE).copy()
 
 
 # ---- handshake accept keys ---------------------------------------------------

@@ -8,6 +8,8 @@
 // on the GPU by cfws_deserialize_* / cfws_pipeline_*. This is the host half
 // of a receive loop whose bytes are in host memory (socket buffers); the
 // device-resident form is cfws_index_frames_batch (cfws_ops.hip).
+// Also the host form of the message and control tables of received frames
+// (cfws_messages_from_frames; device form: cfws_messages.hip).
 #include <cstdint>
 #include <cstring>
 
@@ -102,6 +104,59 @@ size_t cfws_h2_index_frames(const void* h_buf, uint64_t begin, uint64_t end, uin
     if (consumed) *consumed = p;
     if (stop) *stop = st;
     return k;
+}
+
+// The message rule (cfws_rules.h) as a walk: per connection, frames in index
+// order, one message under construction while `open`. The device form
+// (cfws_messages.hip) takes the same decisions from the same functions.
+size_t cfws_messages_from_frames(const cfws_frame_desc_t* h_desc, const int32_t* h_status, size_t n_frames,
+                                 const uint64_t* h_conn_first, size_t n_conns, cfws_message_t* msgs,
+                                 size_t msg_capacity, uint64_t* conn_first_msg, uint32_t* control,
+                                 size_t control_capacity, uint64_t* n_control)
+{
+    const size_t conns = h_conn_first ? n_conns : 1;
+    auto bound = [&](size_t c) -> size_t {        // a value above n_frames is read as n_frames
+        return h_conn_first[c] < n_frames ? (size_t)h_conn_first[c] : n_frames;
+    };
+    size_t m = 0;
+    uint64_t nc = 0;
+    for (size_t c = 0; c < conns; ++c) {
+        const size_t lo = h_conn_first && c ? bound(c) : 0;
+        const size_t hi = h_conn_first && c + 1 < conns ? bound(c + 1) : n_frames;
+        if (conn_first_msg) conn_first_msg[c] = m;
+        cfws_message_t cur = {};
+        bool open = false, lost = false;
+        auto end_message = [&](bool last_fin, bool followed) {
+            cur.flags = (uint8_t)(cur.flags | message_end_flags(last_fin, followed, lost));
+            if (m < msg_capacity) msgs[m] = cur;
+            ++m;
+        };
+        for (size_t f = lo; f < hi; ++f) {
+            const cfws_frame_desc_t& d = h_desc[f];
+            const int32_t st = h_status ? h_status[f] : CFWS_PARSE_COMPLETE;
+            const uint32_t cls = message_frame_class(st, d.opcode);
+            if (cls == kMessageFrameIgnored) continue;
+            if (cls == kMessageFrameControl) {
+                if (nc < control_capacity) control[nc] = (uint32_t)f;
+                ++nc;
+                continue;
+            }
+            if (message_starts(d.opcode, open)) {
+                if (open) end_message(false, true);
+                cur = cfws_message_t{d.payload_off, 0, (uint32_t)f, 0, (uint32_t)c, d.opcode,
+                                     (uint8_t)message_start_flags(d.opcode), 0};
+                lost = false;
+            }
+            cur.payload_size += d.payload_size;
+            ++cur.n_fragments;
+            lost = lost || st == CFWS_ERROR_OUT_OF_MEMORY;
+            open = d.fin == 0;
+            if (!open) end_message(true, false);
+        }
+        if (open) end_message(false, false);
+    }
+    if (n_control) *n_control = nc;
+    return m;
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@
 // relay of received frames; cfws_keys.hip: the mask-key draw;
 // cfws_handshake.hip: the upgrade's keys and their checks; cfws_ops.hip:
 // device indexing, copies, fills and the drop-in service; cfws_h2index.hip:
-// HTTP/2 device indexing).
+// HTTP/2 device indexing; cfws_messages.hip: the message and control tables
+// of received frames).
 // Everything here is internal to each unit (anonymous namespace); what the
 // units share is defined once (namespace cfws_rt): the error state and the
 // pass timing in cfws_device.hip; the deserialize plan, the fused

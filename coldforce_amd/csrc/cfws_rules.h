@@ -144,4 +144,52 @@ __host__ __device__ __forceinline__ bool h2_selected(const H2Hop& h, uint32_t se
     return (select == CFWS_H2_INDEX_ALL || h.type == 0) && (stream_id == 0 || h.stream_id == stream_id);
 }
 
+// The message rule of cfws_messages_from_frames / cfws_messages_batch
+// (include/cfws.h): which received frames make up which message. THIS
+// LIBRARY'S rule, not the reference's: the reference hands every frame to the
+// application as it arrives (examples/ws_client/main.c:50-72; opcodes
+// co_ws_frame.h:28-34) and checks no fragment order. A connection's frames
+// are taken in index order with one bit of state, `open` (a message is
+// unfinished; false at the connection's start):
+//   * message_frame_class: a frame whose header did not parse to a frame is
+//     IGNORED (changes nothing, listed nowhere); opcode >= 8 is CONTROL (its
+//     index goes to the control list, `open` untouched: control frames may
+//     sit between a message's fragments, RFC 6455 5.4); the rest is DATA, the
+//     split CFWS_DESERIALIZE_REASSEMBLE uses;
+//   * message_starts: a data frame starts a message when it carries an opcode
+//     or no message is open, else it joins the open one; then open = !fin;
+//   * message_start_flags: a message started by a CONTINUATION is HEADLESS;
+//   * message_end_flags: a message ends FINAL with a fin fragment, CUT when
+//     another message of its connection starts while it is open, OPEN when
+//     its connection's frames end first; LOST_BYTES when a fragment's status
+//     is OUT_OF_MEMORY.
+// The host form walks with these; the device form (cfws_messages.hip) turns
+// `open` into "the connection's previous data frame's fin" and the rest into
+// sums, and takes every decision from the same four functions.
+enum : uint32_t { kMessageFrameIgnored = 0, kMessageFrameControl = 1, kMessageFrameData = 2 };
+
+__host__ __device__ __forceinline__ uint32_t message_frame_class(int32_t status, uint32_t opcode)
+{
+    if (status != CFWS_PARSE_COMPLETE && status != CFWS_ERROR_OUT_OF_MEMORY) return kMessageFrameIgnored;
+    return opcode >= 8u ? kMessageFrameControl : kMessageFrameData;
+}
+
+__host__ __device__ __forceinline__ bool message_starts(uint32_t opcode, bool open)
+{
+    return opcode != 0u || !open;
+}
+
+__host__ __device__ __forceinline__ uint32_t message_start_flags(uint32_t opcode)
+{
+    return opcode == 0u ? CFWS_MESSAGE_HEADLESS : 0u;
+}
+
+// last_fin: the message's last fragment's fin; followed: another message of
+// the same connection starts after it; lost: a fragment was OUT_OF_MEMORY
+__host__ __device__ __forceinline__ uint32_t message_end_flags(bool last_fin, bool followed, bool lost)
+{
+    return (last_fin ? CFWS_MESSAGE_FINAL : (followed ? CFWS_MESSAGE_CUT : CFWS_MESSAGE_OPEN)) |
+           (lost ? CFWS_MESSAGE_LOST_BYTES : 0u);
+}
+
 #endif
