@@ -7,7 +7,7 @@
 HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_handshake cfws_ops cfws_h2index cfws_messages cfws_uniform
+DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_handshake cfws_ops cfws_h2index cfws_messages cfws_h2streams cfws_uniform
 HOSTSRC  := cfws_frame cfws_pipeline cfws_index cfws_graph
 HDR      := include/cfws.h include/cfws_co_ws_frame.h coldforce_amd/csrc/cfws_internal.h coldforce_amd/csrc/cfws_rules.h coldforce_amd/csrc/cfws_chunks.h coldforce_amd/csrc/cfws_keyrules.h coldforce_amd/csrc/cfws_keydev.h coldforce_amd/csrc/cfws_devpolicy.h
 LIB      := coldforce_amd/libcfws.so
@@ -54,6 +54,12 @@ build/libmsghostwalk.so: tools/messages_host_walk.cpp $(LIB) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -Iinclude -o $@ $< -Lcoldforce_amd -lcfws \
 	    -Wl,-rpath,'$$ORIGIN/../coldforce_amd' -lpthread
 
+# tools/h2_streams_bench.py's host leg (threads of cfws_h2_streams_from_frames calls)
+build/libh2streamshostwalk.so: tools/h2_streams_host_walk.cpp $(LIB) $(HDR)
+	@mkdir -p build
+	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -Iinclude -o $@ $< -Lcoldforce_amd -lcfws \
+	    -Wl,-rpath,'$$ORIGIN/../coldforce_amd' -lpthread
+
 oracle:
 	$(MAKE) -s -C oracle
 
@@ -73,6 +79,15 @@ build/messages_asan: tests/native/messages_asan.cpp coldforce_amd/csrc/cfws_inde
 	$(HIPCC) -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Icoldforce_amd/csrc -o $@ \
 	    tests/native/messages_asan.cpp coldforce_amd/csrc/cfws_index.cpp
+
+# the host stream grouping (cfws_h2_streams_from_frames, cfws_index.cpp alone)
+# in a stand-alone host program under AddressSanitizer + UBSan;
+# tests/test_h2_streams.py builds and runs it
+build/h2_streams_asan: tests/native/h2_streams_asan.cpp coldforce_amd/csrc/cfws_index.cpp $(HDR)
+	@mkdir -p build
+	$(HIPCC) -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Icoldforce_amd/csrc -o $@ \
+	    tests/native/h2_streams_asan.cpp coldforce_amd/csrc/cfws_index.cpp
 
 # the pipeline's chunk cuts (cfws_chunks.h, header only) in a stand-alone host
 # program under AddressSanitizer + UBSan; tests/test_pipeline_chunks.py builds

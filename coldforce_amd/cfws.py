@@ -73,6 +73,8 @@ BATCH_SYMBOLS = (
     "cfws_pipeline_h2_receive",
     "cfws_messages_from_frames", "cfws_messages_workspace_size", "cfws_messages_group_frames",
     "cfws_messages_batch",
+    "cfws_h2_streams_from_frames", "cfws_h2_streams_workspace_size", "cfws_h2_streams_group_frames",
+    "cfws_h2_streams_batch",
 )
 DROPIN_SYMBOLS = (
     "co_ws_frame_serialize", "co_ws_frame_deserialize", "co_ws_frame_create",
@@ -199,6 +201,10 @@ def lib(path: str = LIB_PATH) -> C.CDLL:
         "cfws_messages_group_frames": ([], _sz),
         "cfws_messages_batch": ([_vp, _vp, _sz, _vp, _sz, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _sz, _vp],
                                 C.c_int),
+        "cfws_h2_streams_from_frames": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp], _sz),
+        "cfws_h2_streams_workspace_size": ([_sz, _sz], _sz),
+        "cfws_h2_streams_group_frames": ([], _sz),
+        "cfws_h2_streams_batch": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp], C.c_int),
         "cfws_pipeline_h2_receive": ([_vp, _vp, _u64, _u64, _u32, _u32, _u64, _u32, _vp, _vp, _vp,
                                       C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_u64),
                                       C.POINTER(C.c_int32), _vp, _u64, C.POINTER(_u64)], C.c_int),
@@ -991,6 +997,87 @@ def h2_index_frames_batch(buf_t, begin_t, end_t, max_frame_size: int = H2_DEFAUL
 
 def h2_info_from_device(t) -> np.ndarray:
     return t.cpu().numpy().reshape(-1).view(H2_INFO_DTYPE).copy()
+
+
+# ---- HTTP/2 DATA frames of many streams, by message ---------------------------
+H2_STREAM_CLOSED, H2_STREAM_TAIL, H2_STREAM_FIRST, H2_STREAM_PADDED = 1, 2, 4, 8
+
+# cfws_h2_stream_msg_t, 32 bytes.
+H2_STREAM_MSG_DTYPE = np.dtype([("length_sum", "<u8"), ("first", "<u4"), ("n_data", "<u4"), ("conn", "<u4"),
+                                ("stream_id", "<u4"), ("end_frame", "<u4"), ("flags", "u1"), ("zero8", "u1"),
+                                ("zero16", "<u2")])
+assert H2_STREAM_MSG_DTYPE.itemsize == 32
+
+
+def h2_streams_from_frames(starts: np.ndarray, info: np.ndarray, conn_first: np.ndarray | None = None):
+    """Host stream grouping (cfws_h2_streams_from_frames): (order,
+    order_frame, msgs, conn_first_msg, stream_first, counts). order and
+    order_frame hold counts[1] + counts[3] entries, msgs counts[0] + counts[2],
+    stream_first counts[4]; conn_first_msg is one entry without conn_first."""
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    inf = np.ascontiguousarray(info, dtype=H2_INFO_DTYPE)
+    n = inf.size
+    cf = None if conn_first is None else np.ascontiguousarray(conn_first, dtype=np.uint64)
+    order = np.zeros(max(n, 1), np.uint64)
+    order_frame = np.zeros(max(n, 1), np.uint32)
+    msgs = np.zeros(max(n, 1), H2_STREAM_MSG_DTYPE)
+    cfm = np.zeros(max(1 if cf is None else cf.size, 1), np.uint64)
+    sf = np.zeros(max(n, 1), np.uint64)
+    counts = np.zeros(5, np.uint64)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    m = lib().cfws_h2_streams_from_frames(ptr(st), ptr(inf), n, ptr(cf), 0 if cf is None else cf.size, ptr(order),
+                                          ptr(order_frame), ptr(msgs), ptr(cfm), ptr(sf), ptr(counts))
+    c = [int(x) for x in counts]
+    assert m == c[0]
+    return (order[:c[1] + c[3]], order_frame[:c[1] + c[3]], msgs[:c[0] + c[2]],
+            cfm[:1 if cf is None else cf.size], sf[:c[4]], c)
+
+
+def h2_streams_group_frames() -> int:
+    """DATA records one workgroup of cfws_h2_streams_batch sorts in LDS; a
+    connection that crosses a multiple of it is finished by merge passes."""
+    return int(lib().cfws_h2_streams_group_frames())
+
+
+def h2_streams_workspace(n_frames: int, n_conns: int = 0, device="cuda"):
+    import torch
+    return torch.empty(lib().cfws_h2_streams_workspace_size(n_frames, n_conns), dtype=torch.uint8, device=device)
+
+
+def h2_streams_batch(starts_t, info_t, n: int | None = None, conn_first_t=None, ws_t=None, stream=None,
+                     order_t=None, order_frame_t=None, msgs_t=None, conn_first_msg_t=None, stream_first_t=None,
+                     counts_t=None):
+    """Stream grouping of device-resident records (cfws_h2_streams_batch).
+    starts_t: int64; info_t: (>= n, 16) uint8 rows, as h2_index_frames_batch
+    returns them; n: the records (default: all of starts_t); conn_first_t:
+    that call's first_t or None for one connection. Returns (order_t,
+    order_frame_t, msgs_t, conn_first_msg_t, stream_first_t, counts) --
+    counts (five ints) synchronises. msgs_t: (n, 32) uint8 rows
+    (h2_stream_msgs_from_device). Outputs and workspace are allocated when
+    not given."""
+    import torch
+    n = starts_t.numel() if n is None else n
+    dev = starts_t.device
+    n_conns = 0 if conn_first_t is None else conn_first_t.numel()
+    order_t = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if order_t is None else order_t
+    order_frame_t = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if order_frame_t is None else order_frame_t
+    msgs_t = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev) if msgs_t is None else msgs_t
+    if conn_first_msg_t is None:
+        conn_first_msg_t = torch.empty(max(n_conns, 1), dtype=torch.int64, device=dev)
+    stream_first_t = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if stream_first_t is None else stream_first_t
+    counts_t = torch.zeros(5, dtype=torch.int64, device=dev) if counts_t is None else counts_t
+    if ws_t is None:
+        ws_t = h2_streams_workspace(n, n_conns, dev)
+    _check(lib().cfws_h2_streams_batch(_p(starts_t), _p(info_t), n, _p(conn_first_t), n_conns, _p(order_t),
+                                       _p(order_frame_t), _p(msgs_t), _p(conn_first_msg_t), _p(stream_first_t),
+                                       _p(counts_t), _p(ws_t), ws_t.numel(), _stream(stream)),
+           "cfws_h2_streams_batch")
+    return (order_t, order_frame_t, msgs_t, conn_first_msg_t[:1 if conn_first_t is None else n_conns],
+            stream_first_t, [int(x) for x in counts_t.tolist()])
+
+
+def h2_stream_msgs_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().reshape(-1).view(H2_STREAM_MSG_DTYPE).copy()
 
 
 # ---- message and control tables of received frames ---------------------------

@@ -9,9 +9,13 @@
 // of a receive loop whose bytes are in host memory (socket buffers); the
 // device-resident form is cfws_index_frames_batch (cfws_ops.hip).
 // Also the host form of the message and control tables of received frames
-// (cfws_messages_from_frames; device form: cfws_messages.hip).
+// (cfws_messages_from_frames; device form: cfws_messages.hip), and of the
+// HTTP/2 stream grouping (cfws_h2_streams_from_frames; device form:
+// cfws_h2streams.hip).
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "cfws.h"
 #include "cfws_rules.h"
@@ -157,6 +161,90 @@ size_t cfws_messages_from_frames(const cfws_frame_desc_t* h_desc, const int32_t*
     }
     if (n_control) *n_control = nc;
     return m;
+}
+
+// The stream rule (cfws_rules.h) as a sort and a walk: per connection the
+// pooled records, stably sorted by stream id; every run in that order is a
+// closed message or its stream's tail. Closed messages and their frames go
+// out first, then the tails. The device form (cfws_h2streams.hip) takes the
+// same decisions from the same functions.
+size_t cfws_h2_streams_from_frames(const uint64_t* starts, const cfws_h2_frame_info_t* info, size_t n_frames,
+                                   const uint64_t* conn_first, size_t n_conns, uint64_t* order,
+                                   uint32_t* order_frame, cfws_h2_stream_msg_t* msgs, uint64_t* conn_first_msg,
+                                   uint64_t* stream_first, uint64_t counts[5])
+{
+    const size_t conns = conn_first ? n_conns : 1;
+    auto bound = [&](size_t c) -> size_t {        // a value above n_frames is read as n_frames
+        return conn_first[c] < n_frames ? (size_t)conn_first[c] : n_frames;
+    };
+    struct Run {
+        cfws_h2_stream_msg_t msg;
+        size_t at;                                // its first frame in `sorted`
+    };
+    std::vector<uint32_t> sorted;                 // every connection's pooled records, grouped
+    std::vector<Run> runs;
+    std::vector<uint32_t> one;
+    size_t n_closed = 0, closed_frames = 0;
+    for (size_t c = 0; c < conns; ++c) {
+        const size_t lo = conn_first && c ? bound(c) : 0;
+        const size_t hi = conn_first && c + 1 < conns ? bound(c + 1) : n_frames;
+        if (conn_first_msg) conn_first_msg[c] = n_closed;
+        one.clear();
+        for (size_t f = lo; f < hi; ++f)
+            if (h2_stream_pooled(info[f].type, info[f].stream_id)) one.push_back((uint32_t)f);
+        std::stable_sort(one.begin(), one.end(),
+                         [&](uint32_t a, uint32_t b) { return info[a].stream_id < info[b].stream_id; });
+        bool padded = false, stream_start = false;
+        for (size_t r = 0; r < one.size(); ++r) {
+            const cfws_h2_frame_info_t& i = info[one[r]];
+            const bool same = r > 0 && info[one[r - 1]].stream_id == i.stream_id;
+            if (h2_stream_starts(r == 0, same, r > 0 && h2_stream_closes(info[one[r - 1]].flags))) {
+                runs.push_back(Run{cfws_h2_stream_msg_t{0, 0, 0, (uint32_t)c, i.stream_id, 0, 0, 0, 0},
+                                   sorted.size() + r});
+                padded = false;
+                stream_start = !same;
+            }
+            cfws_h2_stream_msg_t& m = runs.back().msg;
+            m.length_sum += i.length;
+            ++m.n_data;
+            m.end_frame = one[r];
+            padded = padded || (i.flags & kH2FlagPadded) != 0;
+            const bool last = r + 1 == one.size() || info[one[r + 1]].stream_id != i.stream_id;
+            if (h2_stream_closes(i.flags) || last) {
+                m.flags = (uint8_t)h2_stream_msg_flags(h2_stream_closes(i.flags), stream_start, padded);
+                if (m.flags & CFWS_H2_STREAM_CLOSED) {
+                    ++n_closed;
+                    closed_frames += m.n_data;
+                }
+            }
+        }
+        sorted.insert(sorted.end(), one.begin(), one.end());
+    }
+    size_t at[2] = {0, n_closed}, frame_at[2] = {0, closed_frames}, n_streams = 0;
+    for (Run& r : runs) {
+        const int tail = (r.msg.flags & CFWS_H2_STREAM_CLOSED) ? 0 : 1;
+        r.msg.first = (uint32_t)frame_at[tail];
+        for (uint32_t k = 0; k < r.msg.n_data; ++k) {
+            const uint32_t f = sorted[r.at + k];
+            if (order) order[frame_at[tail] + k] = starts[f];
+            if (order_frame) order_frame[frame_at[tail] + k] = f;
+        }
+        if (r.msg.flags & CFWS_H2_STREAM_FIRST) {
+            if (stream_first) stream_first[n_streams] = at[0];
+            ++n_streams;
+        }
+        if (msgs) msgs[at[tail]] = r.msg;
+        ++at[tail];
+        frame_at[tail] += r.msg.n_data;
+    }
+    if (counts) {
+        counts[0] = n_closed;
+        counts[1] = closed_frames;
+        counts[2] = runs.size() - n_closed;
+        counts[3] = sorted.size() - closed_frames;
+        counts[4] = n_streams;
+    }
+    return n_closed;
 }
 
 }  // extern "C"

@@ -192,4 +192,48 @@ __host__ __device__ __forceinline__ uint32_t message_end_flags(bool last_fin, bo
            (lost ? CFWS_MESSAGE_LOST_BYTES : 0u);
 }
 
+// The stream rule of cfws_h2_streams_from_frames / cfws_h2_streams_batch
+// (include/cfws.h): which indexed HTTP/2 records pool into which message. The
+// reference looks a DATA frame's stream up by the id as read
+// (co_http2_client.c:475-476), sends stream 0 to the system handler
+// (:492-495) and pools every other DATA frame in its stream until END_STREAM
+// delivers (co_http2_stream.c:550-608):
+//   * h2_stream_pooled: only DATA (type 0) on a stream other than 0 is pooled;
+//     every other record is ignored;
+//   * a connection's pooled records are taken grouped by stream id (unsigned,
+//     as read), arrival order inside a stream; in that order
+//     h2_stream_starts: a frame starts a message (or the stream's tail) when
+//     it is its connection's first, when the stream changes or when the
+//     frame before it carried END_STREAM (h2_stream_closes);
+//   * a run that ends with END_STREAM is a closed message, any other run is
+//     its stream's tail; h2_stream_msg_flags: a closed message that is the
+//     first run of its (connection, stream) is FIRST, a run with a PADDED
+//     frame (flag 0x8) is PADDED.
+// The host form sorts and walks with these; the device form
+// (cfws_h2streams.hip) sorts, then takes the same decisions per row.
+constexpr uint32_t kH2FlagEndStream = 0x1u, kH2FlagPadded = 0x8u;
+
+__host__ __device__ __forceinline__ bool h2_stream_pooled(uint32_t type, uint32_t stream_id)
+{
+    return type == 0u && stream_id != 0u;
+}
+
+__host__ __device__ __forceinline__ bool h2_stream_closes(uint32_t flags)
+{
+    return (flags & kH2FlagEndStream) != 0u;
+}
+
+__host__ __device__ __forceinline__ bool h2_stream_starts(bool first_of_conn, bool same_stream, bool prev_closes)
+{
+    return first_of_conn || !same_stream || prev_closes;
+}
+
+// closed: the run's last frame closes; stream_start: the run is the first of
+// its (connection, stream); padded: some frame of it has PADDED
+__host__ __device__ __forceinline__ uint32_t h2_stream_msg_flags(bool closed, bool stream_start, bool padded)
+{
+    return (closed ? CFWS_H2_STREAM_CLOSED | (stream_start ? CFWS_H2_STREAM_FIRST : 0u) : CFWS_H2_STREAM_TAIL) |
+           (padded ? CFWS_H2_STREAM_PADDED : 0u);
+}
+
 #endif

@@ -626,6 +626,136 @@ int cfws_h2_index_frames_batch(const void* d_buf, const uint64_t* d_begin, const
                                uint64_t* d_total, void* d_workspace, size_t workspace_size,
                                void* stream);
 
+/* ---- HTTP/2 DATA frames of many streams, by message -------------------------
+ * The step between cfws_h2_index_frames_batch and cfws_h2_deserialize_batch
+ * when a connection carries several streams (RFC 8441: one WebSocket per
+ * stream, so their DATA frames interleave): from the indexed records of all
+ * streams of all connections, one receive index in which every message's DATA
+ * frames are contiguous and end with END_STREAM, which the receive handles as
+ * it is. The calls read the records only, never the receive buffer.
+ *
+ * Input: n_frames records, starts[k] and info[k], as cfws_h2_index_frames /
+ * _batch write them with select ALL or DATA and stream_id 0. Connections as
+ * for cfws_messages_batch: connection c is records [conn_first[c], c + 1 <
+ * n_conns ? conn_first[c + 1] : n_frames) -- the indexer's d_first --
+ * non-decreasing, conn_first[0] == 0, a value above n_frames is read as
+ * n_frames, empty connections allowed, nothing outside the arrays is read
+ * whatever they hold; conn_first == NULL: one connection of all records
+ * (n_conns ignored, conn_first_msg may be NULL and is otherwise one entry).
+ *
+ * The rule (cfws_rules.h: h2_stream_pooled, h2_stream_starts,
+ * h2_stream_msg_flags). co_http2_client_on_tcp_receive_ready
+ * (co_http2_client.c:462-541) looks the stream up by the id as read
+ * (:475-476: the reserved bit is kept, 0x80000001 and 1 are different
+ * streams), sends stream 0 to the system handler (:492-495: never pooled) and
+ * hands every other DATA frame to that stream's pool, in arrival order, until
+ * a frame with END_STREAM delivers the pooled bytes (co_http2_stream.c:550-608).
+ *   * A record with type != 0 or stream_id == 0 is ignored: listed nowhere,
+ *     changes nothing.
+ *   * A connection's other records are grouped by stream_id, arrival order
+ *     kept inside each stream. In one stream's sequence every frame with
+ *     END_STREAM (flags & 1) closes a message: the frames since the previous
+ *     close, or since the stream's first frame in this call (an END_STREAM
+ *     frame of length 0 alone is a message of one frame). The frames after the
+ *     stream's last END_STREAM are its tail: pooled, not delivered.
+ * The ORDER is this library's: closed messages by connection, then stream_id
+ * ascending as an unsigned 32-bit value, then arrival; tails by connection,
+ * then stream_id. (The reference delivers a connection's messages in the
+ * order of their END_STREAM frames: sort by end_frame for that.) Stream state
+ * is not modelled (unknown or closed streams, which the reference drops,
+ * :478-484; flow-control resets, co_http2_stream.c:497-507): the records name
+ * connection and stream, so the caller drops what it does not know. A stream
+ * whose pool was open at the end of the previous call continues in this one
+ * when the caller carried its tail; the tables describe this
+ * call's frames only.
+ *
+ * Outputs; no capacities: order, order_frame and msgs have room for n_frames
+ * entries, and nothing past the counts is written.
+ *   counts[0] closed messages M      counts[1] their frames F
+ *   counts[2] tails T                counts[3] the tails' frames
+ *   counts[4] streams with at least one closed message
+ *   msgs[0, M) the closed messages, msgs[M, M + T) the tails.
+ *   order[0, F): the starts[] values of the closed messages' frames, copied
+ *     as 64-bit values, message after message: with n = F a valid d_h2_index
+ *     of cfws_h2_deserialize_batch over the same arena, whose message row m
+ *     is msgs[m] and whose *n_messages is M. order[F, F + counts[3]): the
+ *     tails' frames the same way (a tail's `first` is a position in order too).
+ *   order_frame (may be NULL): the same positions as record indices.
+ *   conn_first_msg[c] (may be NULL without conn_first): index of c's first
+ *     closed message, the exclusive prefix sum of the per-connection counts.
+ *   stream_first[s] (may be NULL; room for n_frames entries): index of the
+ *     first closed message of the s-th stream that has one, in table order:
+ *     what cfws_messages_batch takes as d_conn_first over the receive's
+ *     d_msg_desc, so that WS fragments arriving as separate
+ *     END_STREAM-delimited messages of one stream are joined per stream.
+ * Host form: on the calling thread (it allocates its sort's scratch); returns
+ * M. */
+#define CFWS_H2_STREAM_CLOSED  1u   /* ends with END_STREAM: a message            */
+#define CFWS_H2_STREAM_TAIL    2u   /* the stream's frames after its last close   */
+#define CFWS_H2_STREAM_FIRST   4u   /* first closed message of its (conn, stream) */
+#define CFWS_H2_STREAM_PADDED  8u   /* some frame has PADDED: length_sum is an
+                                       upper bound of the pooled bytes, else exact */
+typedef struct cfws_h2_stream_msg {   /* 32 bytes, two 16-byte stores */
+    uint64_t length_sum;   /* sum of the frames' info.length */
+    uint32_t first;        /* position of its first frame in d_order */
+    uint32_t n_data;       /* its DATA frames */
+    uint32_t conn;         /* 0 without conn_first */
+    uint32_t stream_id;    /* as read */
+    uint32_t end_frame;    /* record index (into starts/info) of its last frame */
+    uint8_t  flags, zero8; uint16_t zero16;
+} cfws_h2_stream_msg_t;
+
+size_t cfws_h2_streams_from_frames(const uint64_t* starts, const cfws_h2_frame_info_t* info,
+        size_t n_frames, const uint64_t* conn_first, size_t n_conns,
+        uint64_t* order, uint32_t* order_frame, cfws_h2_stream_msg_t* msgs,
+        uint64_t* conn_first_msg, uint64_t* stream_first, uint64_t counts[5]);
+
+/* Device form: the same tables from device-resident records, so that an
+ * HTTP/2 tick is index -> group -> one receive -> message tables:
+ * cfws_h2_index_frames_batch -> cfws_h2_streams_batch (d_first as
+ * d_conn_first) -> read the counts -> one cfws_h2_deserialize_batch over
+ * d_order[0, F) -> cfws_messages_batch with d_stream_first. d_msgs must be
+ * 16-byte aligned. Nothing is allocated and nothing synchronises; not a timed
+ * pass (a pending cfws_time_next_pass pair is dropped); every launch is a
+ * plain kernel on `stream` (no look-back between workgroups; their number
+ * depends on n_frames alone), so the call can be captured. The result does
+ * not depend on what the workspace or the outputs held. Errors, device check
+ * first: null d_starts, d_info, d_order or d_msgs (n_frames > 0), d_counts or
+ * workspace, d_conn_first_msg (with d_conn_first), a misaligned d_msgs,
+ * n_frames > 2^32 - 1 -> CFWS_ERROR_INVALID_ARGUMENT; workspace too small ->
+ * CFWS_ERROR_WORKSPACE; nothing is written. n_frames == 0 writes five zero
+ * counts and d_conn_first_msg[c] = 0 for every c.
+ * The grouping is a stable sort of each connection's DATA records by
+ * (stream_id, arrival). The DATA records are compacted into a dense list
+ * (connections stay contiguous); every aligned block of
+ * cfws_h2_streams_group_frames() dense rows is sorted in LDS by (connection,
+ * stream_id, arrival), a bitonic network, which finishes every connection
+ * that lies inside one block -- small connections share a workgroup. A
+ * connection that crosses a block boundary, as every connection of more than
+ * cfws_h2_streams_group_frames() DATA records does, is finished in the
+ * workspace: merge passes over its block pieces (run lengths G, 2G, 4G, ...;
+ * each key finds its place by a binary search in the sibling run), so a
+ * connection of n records costs about n log2(G)^2 / 4 compare-exchanges and
+ * at most log2(n / G) + 2 passes of n log2(n) key comparisons whatever the
+ * peer interleaves: no path is quadratic, and none ranks by counting. The workspace (cfws_h2_streams_workspace_size) is 76 bytes per
+ * record (a 16-byte dense row, three 8-byte key arrays, a 4-byte message
+ * index and a 32-byte row per message) and 4 bytes per connection.
+ * Speed (profiles/h2streams/h2_streams_bench.jsonl):
+ * 16,384 connections x 62 records over 4 streams take 0.27 ms, 16,384 x 3
+ * records on one stream 0.15 ms (its 18 launches) and one connection of 2^20
+ * records, each its own stream, 0.38 ms: 13 to 32 times what cfws_device_copy
+ * takes for the bytes the call must move (24 per record in, 12 per frame and
+ * 32 per message out), and 10, 3.5 and 120 times faster than copying the
+ * records to pinned memory and running cfws_h2_streams_from_frames on 16
+ * threads (2.7, 0.5 and 46 ms). The device form lost at no shape. */
+size_t cfws_h2_streams_workspace_size(size_t n_frames, size_t n_conns);
+size_t cfws_h2_streams_group_frames(void);
+int cfws_h2_streams_batch(const uint64_t* d_starts, const cfws_h2_frame_info_t* d_info,
+        size_t n_frames, const uint64_t* d_conn_first, size_t n_conns,
+        uint64_t* d_order, uint32_t* d_order_frame, cfws_h2_stream_msg_t* d_msgs,
+        uint64_t* d_conn_first_msg, uint64_t* d_stream_first, uint64_t* d_counts,
+        void* d_workspace, size_t workspace_size, void* stream);
+
 /* ---- message and control tables of received frames --------------------------
  * What an application consumes after a receive: where each message starts,
  * how long it is, what it is and whether it is whole, and which frames are
