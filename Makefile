@@ -31,7 +31,7 @@ build/examples/batch_roundtrip: examples/batch_roundtrip.c $(LIB) $(HDR)
 	    -Lcoldforce_amd -lcfws -L/opt/rocm/lib -lamdhip64 \
 	    -Wl,-rpath,'$$ORIGIN/../../coldforce_amd' -Wl,-rpath,/opt/rocm/lib
 
-$(OBJDIR)/%.o: coldforce_amd/csrc/%.hip $(HDR) coldforce_amd/csrc/cfws_kernels.h
+$(OBJDIR)/%.o: coldforce_amd/csrc/%.hip $(HDR) coldforce_amd/csrc/cfws_kernels.h coldforce_amd/csrc/cfws_tables.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) --offload-arch=$(ARCH) $(HIPFLAGS) -Iinclude -Icoldforce_amd/csrc -c $< -o $@
 
@@ -101,7 +101,7 @@ build/chunks_test: tests/native/chunks_test.cpp $(HDR)
 ref: all
 	$(MAKE) -s -C oracle ref
 
-asm: $(HDR) coldforce_amd/csrc/cfws_kernels.h
+asm: $(HDR) coldforce_amd/csrc/cfws_kernels.h coldforce_amd/csrc/cfws_tables.h
 	@mkdir -p $(OBJDIR)/asm
 	rm -f $(OBJDIR)/asm/resource-usage.txt
 	for d in $(DEVSRC); do $(HIPCC) --offload-arch=$(ARCH) $(HIPFLAGS) -Iinclude -Icoldforce_amd/csrc -c coldforce_amd/csrc/$$d.hip -o $(OBJDIR)/asm/$$d.o \

@@ -2,14 +2,16 @@
 // the device (cfws_h2_streams_batch, include/cfws.h). The
 // rule is written once (cfws_rules.h: h2_stream_pooled, h2_stream_starts,
 // h2_stream_closes, h2_stream_msg_flags) and shared with the host form
-// (cfws_index.cpp). A unit of its own: no existing path changes.
+// (cfws_index.cpp). The three table passes (StRecords, StRuns, StClosed) are
+// one struct each, their reduce and apply kernels one template over it
+// (cfws_tables.h); the rest are plain kernels.
 //
 // Every launch is a plain kernel; their number depends on n_frames alone.
-//   A      pooled records (DATA, stream != 0) compacted into a dense list of
-//          16-byte rows (stream id, record index, length, flags): reduce ->
-//          scan_partials_kernel -> apply, as cfws_messages.hip. Connections
-//          stay contiguous; one thread per connection finds its first dense
-//          row (a search over the rows' record indices).
+//   StRecords  pooled records (DATA, stream != 0) compacted into a dense list
+//          of 16-byte rows (stream id, record index, length, flags): reduce
+//          -> scan_partials_kernel -> apply. Connections stay contiguous; one
+//          thread per connection finds its first dense row (a search over the
+//          rows' record indices).
 //   group  a stable sort of each connection's rows by stream id. The keys are
 //          unique (stream id << 32 | dense row), so any sorting network is
 //          stable. Every aligned tile of kSortTile rows is sorted in LDS by
@@ -25,22 +27,20 @@
 //          between two key arrays and lands in a third, so connections that
 //          are finished are not copied again; a tile none of whose
 //          connections takes part in a pass leaves it at once.
-//   B      over the grouped keys, where a frame's predecessor is the row
+//   StRuns  over the grouped keys, where a frame's predecessor is the row
 //          before it: run starts, running length and PADDED sums (reduce ->
 //          scan_partials2_kernel -> apply); a 32-byte row per run and each
 //          grouped row's run.
-//   C      over the runs: closed (the last frame has END_STREAM) or tail;
+//   StClosed  over the runs: closed (the last frame has END_STREAM) or tail;
 //          closed runs, their frames and FIRST flags summed the same way; the
 //          apply writes the records (closed first, tails after), stream_first
 //          and the counts, and leaves each run's place in d_order.
 //   order  one thread per grouped row: d_order, d_order_frame.
 //   conn   one thread per connection: its first closed message.
-#include "cfws_kernels.h"
+#include "cfws_tables.h"
 
 namespace {
 
-constexpr int kStItems = 4;                                     // consecutive rows per thread
-constexpr uint64_t kStGroup = uint64_t(kThreads) * kStItems;    // rows per workgroup of the table passes
 constexpr uint32_t kSortBits = 11;
 constexpr uint32_t kSortTile = 1u << kSortBits;                 // rows one workgroup sorts in LDS
 constexpr int kSortPer = kSortTile / kThreads;                  // rows per thread of the sort
@@ -48,22 +48,18 @@ constexpr int kSortPer = kSortTile / kThreads;                  // rows per thre
 // ws header words (u64): the scans' grand totals
 enum : int { kHdrData = 0, kHdrRuns = 1, kHdrBytes = 2, kHdrClosed = 3, kHdrClosedFrames = 4 };
 
-// Two counts of at most n_frames <= 2^32 - 1 each in one sum.
-__host__ __device__ inline uint64_t pack2(uint32_t lo, uint32_t hi) { return lo | uint64_t(hi) << 32; }
-
 struct StLayout {
-    uint64_t hdr, part[4], dense, keys[3], run_of, runs, tile_passes, dfirst, bytes;
+    TableHead t;
+    uint64_t keys[3], run_of, runs, tile_passes, dfirst, bytes;
     uint32_t passes;       // merge passes: tiles of kSortTile -> one run of n rows
 };
 
 inline StLayout st_layout(uint64_t n, uint64_t conns)
 {
     StLayout L;
-    const uint64_t nb = grid_for(n, kStGroup), tiles = grid_for(n, kSortTile);
-    uint64_t at = 0;
-    L.hdr = at; at += 256;
-    for (int p = 0; p < 4; ++p) { L.part[p] = at; at = align_up(at + 8 * (nb + 1), 256); }
-    L.dense = at; at = align_up(at + 16 * n, 256);
+    const uint64_t tiles = grid_for(n, kSortTile);
+    L.t = table_head(n);
+    uint64_t at = L.t.end;
     for (int p = 0; p < 3; ++p) { L.keys[p] = at; at = align_up(at + 8 * n, 256); }
     L.run_of = at; at = align_up(at + 4 * n, 256);
     L.runs = at; at = align_up(at + 32 * n, 256);
@@ -90,50 +86,32 @@ static_assert(sizeof(RunRow) == 32 && sizeof(cfws_h2_stream_msg_t) == 32 && size
               "two 16-byte words each; one");
 
 // Record f's dense row; is it pooled?
-__device__ __forceinline__ bool pooled_row(const cfws_h2_frame_info_t* __restrict__ info, uint64_t f, u32x4* row)
+struct PooledRow {
+    bool pooled;
+    u32x4 row;
+};
+
+__device__ __forceinline__ PooledRow pooled_row(const cfws_h2_frame_info_t* __restrict__ info, uint64_t f)
 {
     const cfws_h2_frame_info_t i = info[f];
-    *row = u32x4{i.stream_id, (uint32_t)f, i.length, i.flags};
-    return h2_stream_pooled(i.type, i.stream_id);
+    return {h2_stream_pooled(i.type, i.stream_id), u32x4{i.stream_id, (uint32_t)f, i.length, i.flags}};
 }
 
-// A: per-group counts of pooled records.
-__global__ void __launch_bounds__(kThreads)
-h2streams_count_kernel(const cfws_h2_frame_info_t* __restrict__ info, uint64_t n, uint64_t* __restrict__ part)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t f0 = uint64_t(blockIdx.x) * kStGroup + uint64_t(threadIdx.x) * kStItems;
-    uint64_t x = 0;
-    u32x4 row;
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i)
-        if (f0 + i < n && pooled_row(info, f0 + i, &row)) ++x;
-    uint64_t total;
-    block_exclusive_scan(x, s_wave, &total);
-    if (threadIdx.x == 0) part[blockIdx.x] = total;
-}
+// Over the records: the dense rows of the pooled ones.
+struct StRecords {
+    const cfws_h2_frame_info_t* info;
+    uint64_t n;
+    uint64_t* part[1];
+    u32x4* dense;
 
-// A's apply: the dense rows.
-__global__ void __launch_bounds__(kThreads)
-h2streams_compact_kernel(const cfws_h2_frame_info_t* __restrict__ info, uint64_t n,
-                         const uint64_t* __restrict__ part, u32x4* __restrict__ dense)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t f0 = uint64_t(blockIdx.x) * kStGroup + uint64_t(threadIdx.x) * kStItems;
-    u32x4 row[kStItems];
-    bool keep[kStItems];
-    uint64_t x = 0;
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i) {
-        keep[i] = f0 + i < n && pooled_row(info, f0 + i, &row[i]);
-        x += keep[i] ? 1u : 0u;
+    __device__ TableRows counts() const { return {n}; }
+    __device__ PooledRow load(TableRows, uint64_t f) const { return pooled_row(info, f); }
+    __device__ TableSums<1> weigh(const PooledRow& it) const { return {{it.pooled ? 1u : 0u}}; }
+    __device__ void emit(TableRows, uint64_t, const PooledRow& it, const uint64_t* run) const
+    {
+        if (it.pooled) dense[run[0]] = it.row;
     }
-    uint64_t total;
-    uint64_t k = part[blockIdx.x] + block_exclusive_scan(x, s_wave, &total);
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i)
-        if (keep[i]) dense[k++] = row[i];
-}
+};
 
 // One thread per connection boundary c <= conns: dfirst[c], the dense rows of
 // the connections before c (the first row whose record is at or past
@@ -146,18 +124,12 @@ h2streams_conn_rows_kernel(const u32x4* __restrict__ dense, const uint64_t* __re
 {
     const uint64_t c = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
     if (c > conns) return;
-    const uint64_t nd = hdr[kHdrData];
-    uint64_t lo = 0, hi = nd;
-    if (c == 0) hi = 0;
-    else if (c == conns) lo = nd;
-    else {
+    uint64_t at = c == 0 ? 0 : hdr[kHdrData];
+    if (c != 0 && c != conns) {
         const uint64_t v = conn_first[c], b = v < n ? v : n;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (dense[mid].y < b) lo = mid + 1; else hi = mid;
-        }
+        at = lower_bound(0, at, [&](uint64_t k) { return dense[k].y < b; });
     }
-    dfirst[c] = (uint32_t)lo;
+    dfirst[c] = (uint32_t)at;
 }
 
 // The connection of dense position i < nd: the last c with dfirst[c] <= i, its
@@ -167,12 +139,8 @@ h2streams_conn_rows_kernel(const u32x4* __restrict__ dense, const uint64_t* __re
 __device__ __forceinline__ uint32_t conn_range(const uint32_t* __restrict__ dfirst, uint64_t conns, uint32_t i,
                                                uint32_t* lo, uint32_t* hi)
 {
-    uint64_t a = 0, b = conns;
-    while (a < b) {
-        const uint64_t mid = (a + b) >> 1;
-        if (dfirst[mid] <= i) a = mid + 1; else b = mid;
-    }
-    const uint64_t c = a ? a - 1 : 0;
+    const uint64_t after = lower_bound(0, conns, [&](uint64_t k) { return dfirst[k] <= i; });
+    const uint64_t c = after ? after - 1 : 0;
     *lo = dfirst[c];
     *hi = dfirst[c + 1];
     if (!(*lo <= i && i < *hi)) {
@@ -263,12 +231,8 @@ h2streams_sort_kernel(const u32x4* __restrict__ dense, const uint64_t* __restric
 __device__ __forceinline__ uint64_t keys_below(const uint64_t* __restrict__ src, uint64_t lo, uint64_t hi,
                                                uint64_t key)
 {
-    uint64_t a = lo, b = hi;
-    while (a < b) {
-        const uint64_t mid = (a + b) >> 1;
-        if (src[mid] < key) a = mid + 1; else b = mid;
-    }
-    return a > lo ? a - lo : 0;
+    const uint64_t at = lower_bound(lo, hi, [&](uint64_t k) { return src[k] < key; });
+    return at > lo ? at - lo : 0;
 }
 
 // group, merge pass `pass`: one thread per dense position. In the aligned
@@ -335,81 +299,47 @@ __device__ __forceinline__ RunStart run_start(const u32x4* __restrict__ dense, c
     return s;
 }
 
-// B: per-group sums over the grouped rows: run starts | PADDED rows, lengths.
-__global__ void __launch_bounds__(kThreads)
-h2streams_starts_kernel(const u32x4* __restrict__ dense, const uint64_t* __restrict__ keys,
-                        const uint64_t* __restrict__ hdr, const uint32_t* __restrict__ dfirst, uint64_t conns,
-                        uint64_t* __restrict__ part_counts, uint64_t* __restrict__ part_bytes)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t nd = hdr[kHdrData];
-    const uint64_t r0 = uint64_t(blockIdx.x) * kStGroup + uint64_t(threadIdx.x) * kStItems;
-    uint64_t counts = 0, bytes = 0;
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i) {
-        if (r0 + i < nd) {
-            const u32x4 row = grouped_row(dense, keys, nd, r0 + i);
-            const RunStart s = run_start(dense, keys, nd, r0 + i, row, dfirst, conns);
-            counts += pack2(s.starts ? 1u : 0u, (row.w & kH2FlagPadded) ? 1u : 0u);
-            bytes += row.z;
-        }
-    }
-    uint64_t total_counts, total_bytes;
-    block_exclusive_scan(counts, s_wave, &total_counts);
-    block_exclusive_scan(bytes, s_wave, &total_bytes);
-    if (threadIdx.x == 0) {
-        part_counts[blockIdx.x] = total_counts;
-        part_bytes[blockIdx.x] = total_bytes;
-    }
-}
+// Over the grouped rows: each start's run index and row of running sums; each
+// row's run.
+struct StRuns {
+    struct Item { u32x4 row; RunStart s; };
+    const u32x4* dense;
+    const uint64_t* keys;
+    const uint64_t* hdr;
+    const uint32_t* dfirst;
+    uint64_t conns;
+    uint64_t* part[2];
+    RunRow* runs;
+    uint32_t* run_of;
 
-// B's apply: each start's run index and row of running sums; each row's run.
-__global__ void __launch_bounds__(kThreads)
-h2streams_runs_kernel(const u32x4* __restrict__ dense, const uint64_t* __restrict__ keys,
-                      const uint64_t* __restrict__ hdr, const uint32_t* __restrict__ dfirst, uint64_t conns,
-                      const uint64_t* __restrict__ part_counts, const uint64_t* __restrict__ part_bytes,
-                      RunRow* __restrict__ runs, uint32_t* __restrict__ run_of)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t nd = hdr[kHdrData];
-    const uint64_t r0 = uint64_t(blockIdx.x) * kStGroup + uint64_t(threadIdx.x) * kStItems;
-    u32x4 row[kStItems];
-    RunStart s[kStItems];
-    uint64_t counts = 0, bytes = 0;
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i) {
-        row[i] = u32x4{0, 0, 0, 0};
-        s[i] = RunStart{false, false, 0};
-        if (r0 + i < nd) {
-            row[i] = grouped_row(dense, keys, nd, r0 + i);
-            s[i] = run_start(dense, keys, nd, r0 + i, row[i], dfirst, conns);
-            counts += pack2(s[i].starts ? 1u : 0u, (row[i].w & kH2FlagPadded) ? 1u : 0u);
-            bytes += row[i].z;
-        }
+    __device__ TableRows counts() const { return {hdr[kHdrData]}; }
+    __device__ Item load(TableRows c, uint64_t r) const
+    {
+        const u32x4 row = grouped_row(dense, keys, c.n, r);
+        return {row, run_start(dense, keys, c.n, r, row, dfirst, conns)};
     }
-    uint64_t total;
-    uint64_t c = part_counts[blockIdx.x] + block_exclusive_scan(counts, s_wave, &total);
-    uint64_t b = part_bytes[blockIdx.x] + block_exclusive_scan(bytes, s_wave, &total);
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i) {
-        if (r0 + i < nd) {
-            if (s[i].starts) {
-                u32x4* out = reinterpret_cast<u32x4*>(runs + (c & 0xffffffffu));
-                out[0] = u32x4{(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)(r0 + i), (uint32_t)(c >> 32)};
-                out[1] = u32x4{s[i].conn, s[i].stream_start ? 1u : 0u, 0u, 0u};
-            }
-            c += pack2(s[i].starts ? 1u : 0u, (row[i].w & kH2FlagPadded) ? 1u : 0u);
-            b += row[i].z;
-            run_of[r0 + i] = (uint32_t)c - 1u;          // row 0 starts a run: c >= 1 here
-        }
+    __device__ TableSums<2> weigh(const Item& it) const     // run starts | PADDED rows, lengths
+    {
+        return {{pack2(it.s.starts ? 1u : 0u, (it.row.w & kH2FlagPadded) ? 1u : 0u), it.row.z}};
     }
-}
+    __device__ void emit(TableRows, uint64_t r, const Item& it, const uint64_t* run) const
+    {
+        if (it.s.starts) {
+            u32x4* out = reinterpret_cast<u32x4*>(runs + (run[0] & 0xffffffffu));
+            out[0] = u32x4{(uint32_t)run[1], (uint32_t)(run[1] >> 32), (uint32_t)r, (uint32_t)(run[0] >> 32)};
+            out[1] = u32x4{it.s.conn, it.s.stream_start ? 1u : 0u, 0u, 0u};
+        }
+        // every row, by the starts up to and including it (row 0 starts a run: >= 1)
+        run_of[r] = (uint32_t)(run[0] + weigh(it).v[0]) - 1u;
+    }
+};
 
 // Run u from its row and the next run's (or the grand totals).
 struct RunView {
     uint64_t length_sum;
     uint32_t r, n_data, conn, stream_id, end_frame, flags;
-    bool closed, first;
+    __device__ bool closed() const { return (flags & CFWS_H2_STREAM_CLOSED) != 0; }
+    __device__ bool first() const { return (flags & CFWS_H2_STREAM_FIRST) != 0; }
 };
 
 __device__ __forceinline__ RunView run_view(const u32x4* __restrict__ dense, const uint64_t* __restrict__ keys,
@@ -435,93 +365,57 @@ __device__ __forceinline__ RunView run_view(const u32x4* __restrict__ dense, con
     v.conn = b.x;
     v.stream_id = last.x;
     v.end_frame = last.y;
-    v.closed = h2_stream_closes(last.w);
-    v.flags = h2_stream_msg_flags(v.closed, b.y != 0, next_padded != a.w);
-    v.first = (v.flags & CFWS_H2_STREAM_FIRST) != 0;
+    v.flags = h2_stream_msg_flags(h2_stream_closes(last.w), b.y != 0, next_padded != a.w);
     return v;
 }
 
-// C: per-group sums over the runs: closed runs | FIRST runs, closed frames.
-__global__ void __launch_bounds__(kThreads)
-h2streams_closed_kernel(const u32x4* __restrict__ dense, const uint64_t* __restrict__ keys,
-                        const RunRow* __restrict__ runs, const uint64_t* __restrict__ hdr,
-                        uint64_t* __restrict__ part_counts, uint64_t* __restrict__ part_frames)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t n_runs = hdr[kHdrRuns] & 0xffffffffu;
-    const uint64_t u0 = uint64_t(blockIdx.x) * kStGroup + uint64_t(threadIdx.x) * kStItems;
-    uint64_t counts = 0, frames = 0;
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i) {
-        if (u0 + i < n_runs) {
-            const RunView v = run_view(dense, keys, runs, hdr, u0 + i, n_runs);
-            counts += pack2(v.closed ? 1u : 0u, v.first ? 1u : 0u);
-            frames += v.closed ? v.n_data : 0u;
-        }
-    }
-    uint64_t total_counts, total_frames;
-    block_exclusive_scan(counts, s_wave, &total_counts);
-    block_exclusive_scan(frames, s_wave, &total_frames);
-    if (threadIdx.x == 0) {
-        part_counts[blockIdx.x] = total_counts;
-        part_frames[blockIdx.x] = total_frames;
-    }
-}
+// Over the runs: the records (closed runs from msgs[0], tails from msgs[M]),
+// stream_first, each run's place in d_order and the closed runs before it.
+struct StClosed {
+    struct Counts { uint64_t n, data, closed, first, closed_frames; };  // n: the runs
+    const u32x4* dense;
+    const uint64_t* keys;
+    RunRow* runs;
+    const uint64_t* hdr;
+    uint64_t* part[2];
+    cfws_h2_stream_msg_t* msgs;
+    uint64_t* stream_first;
+    uint64_t* out_counts;
 
-// C's apply: the records (closed runs from msgs[0], tails from msgs[M]),
-// stream_first, each run's place in d_order and the closed runs before it;
-// thread 0 writes the counts.
-__global__ void __launch_bounds__(kThreads)
-h2streams_records_kernel(const u32x4* __restrict__ dense, const uint64_t* __restrict__ keys,
-                         RunRow* __restrict__ runs, const uint64_t* __restrict__ hdr,
-                         const uint64_t* __restrict__ part_counts, const uint64_t* __restrict__ part_frames,
-                         cfws_h2_stream_msg_t* __restrict__ msgs, uint64_t* __restrict__ stream_first,
-                         uint64_t* __restrict__ out_counts)
-{
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t nd = hdr[kHdrData], n_runs = hdr[kHdrRuns] & 0xffffffffu;
-    const uint64_t n_closed = hdr[kHdrClosed] & 0xffffffffu, closed_frames = hdr[kHdrClosedFrames];
-    const uint64_t u0 = uint64_t(blockIdx.x) * kStGroup + uint64_t(threadIdx.x) * kStItems;
-    if (u0 == 0) {
-        out_counts[0] = n_closed;
-        out_counts[1] = closed_frames;
-        out_counts[2] = n_runs - n_closed;
-        out_counts[3] = nd - closed_frames;
-        out_counts[4] = hdr[kHdrClosed] >> 32;
+    __device__ Counts counts() const
+    {
+        return {hdr[kHdrRuns] & 0xffffffffu, hdr[kHdrData], hdr[kHdrClosed] & 0xffffffffu, hdr[kHdrClosed] >> 32,
+                hdr[kHdrClosedFrames]};
     }
-    RunView v[kStItems];
-    uint64_t counts = 0, frames = 0;
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i) {
-        v[i] = RunView{};
-        if (u0 + i < n_runs) {
-            v[i] = run_view(dense, keys, runs, hdr, u0 + i, n_runs);
-            counts += pack2(v[i].closed ? 1u : 0u, v[i].first ? 1u : 0u);
-            frames += v[i].closed ? v[i].n_data : 0u;
-        }
+    __device__ RunView load(const Counts& c, uint64_t u) const { return run_view(dense, keys, runs, hdr, u, c.n); }
+    __device__ TableSums<2> weigh(const RunView& v) const   // closed runs | FIRST runs, closed frames
+    {
+        return {{pack2(v.closed() ? 1u : 0u, v.first() ? 1u : 0u), v.closed() ? v.n_data : 0u}};
     }
-    uint64_t total;
-    uint64_t c = part_counts[blockIdx.x] + block_exclusive_scan(counts, s_wave, &total);
-    uint64_t fr = part_frames[blockIdx.x] + block_exclusive_scan(frames, s_wave, &total);
-#pragma unroll
-    for (int i = 0; i < kStItems; ++i) {
-        if (u0 + i < n_runs) {
-            const uint64_t closed_before = c & 0xffffffffu;
-            // closed: after the closed frames before it; a tail: after all
-            // closed frames and the tail frames before it
-            const uint64_t m = v[i].closed ? closed_before : n_closed + (u0 + i - closed_before);
-            const uint64_t base = v[i].closed ? fr : closed_frames + (v[i].r - fr);
-            u32x4* out = reinterpret_cast<u32x4*>(msgs + m);
-            out[0] = u32x4{(uint32_t)v[i].length_sum, (uint32_t)(v[i].length_sum >> 32), (uint32_t)base, v[i].n_data};
-            out[1] = u32x4{v[i].conn, v[i].stream_id, v[i].end_frame, v[i].flags};
-            if (v[i].first && stream_first) stream_first[c >> 32] = closed_before;
-            runs[u0 + i].base = (uint32_t)base;
-            runs[u0 + i].closed_before = (uint32_t)closed_before;
-            c += pack2(v[i].closed ? 1u : 0u, v[i].first ? 1u : 0u);
-            fr += v[i].closed ? v[i].n_data : 0u;
-        }
+    __device__ void emit(const Counts& c, uint64_t u, const RunView& v, const uint64_t* run) const
+    {
+        const uint64_t closed_before = run[0] & 0xffffffffu;
+        // closed: after the closed frames before it; a tail: after all
+        // closed frames and the tail frames before it
+        const uint64_t m = v.closed() ? closed_before : c.closed + (u - closed_before);
+        const uint64_t base = v.closed() ? run[1] : c.closed_frames + (v.r - run[1]);
+        u32x4* out = reinterpret_cast<u32x4*>(msgs + m);
+        out[0] = u32x4{(uint32_t)v.length_sum, (uint32_t)(v.length_sum >> 32), (uint32_t)base, v.n_data};
+        out[1] = u32x4{v.conn, v.stream_id, v.end_frame, v.flags};
+        if (v.first() && stream_first) stream_first[run[0] >> 32] = closed_before;
+        runs[u].base = (uint32_t)base;
+        runs[u].closed_before = (uint32_t)closed_before;
     }
-}
+    // the counts, also when nothing is pooled and no run exists
+    __device__ void first_thread(const Counts& c) const
+    {
+        out_counts[0] = c.closed;
+        out_counts[1] = c.closed_frames;
+        out_counts[2] = c.n - c.closed;
+        out_counts[3] = c.data - c.closed_frames;
+        out_counts[4] = c.first;
+    }
+};
 
 // One thread per grouped row: its frame's place in d_order.
 __global__ void __launch_bounds__(kThreads)
@@ -540,7 +434,8 @@ h2streams_order_kernel(const uint64_t* __restrict__ starts, const u32x4* __restr
     if (order_frame) order_frame[at] = f;
 }
 
-// One thread per connection: the closed messages of the connections before it.
+// One thread per connection: the closed messages of the connections before it
+// (those before the first run whose connection is >= c).
 __global__ void __launch_bounds__(kThreads)
 h2streams_conn_kernel(const RunRow* __restrict__ runs, const uint64_t* __restrict__ hdr, uint64_t conns,
                       uint64_t* __restrict__ conn_first_msg)
@@ -548,12 +443,8 @@ h2streams_conn_kernel(const RunRow* __restrict__ runs, const uint64_t* __restric
     const uint64_t c = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
     if (c >= conns) return;
     const uint64_t n_runs = hdr[kHdrRuns] & 0xffffffffu;
-    uint64_t lo = 0, hi = n_runs;
-    while (lo < hi) {                           // the first run whose connection is >= c
-        const uint64_t mid = (lo + hi) >> 1;
-        if (runs[mid].conn < c) lo = mid + 1; else hi = mid;
-    }
-    conn_first_msg[c] = lo < n_runs ? runs[lo].closed_before : hdr[kHdrClosed] & 0xffffffffu;
+    const uint64_t u = lower_bound(0, n_runs, [&](uint64_t k) { return runs[k].conn < c; });
+    conn_first_msg[c] = u < n_runs ? runs[u].closed_before : hdr[kHdrClosed] & 0xffffffffu;
 }
 
 }  // namespace
@@ -594,12 +485,10 @@ int cfws_h2_streams_batch(const uint64_t* d_starts, const cfws_h2_frame_info_t* 
         return launch_check("h2 streams");
     }
     const StLayout L = st_layout(n, conns);
-    uint64_t* hdr = ws_ptr<uint64_t>(ws, L.hdr);
-    uint64_t* p0 = ws_ptr<uint64_t>(ws, L.part[0]);
-    uint64_t* p1 = ws_ptr<uint64_t>(ws, L.part[1]);
-    uint64_t* p2 = ws_ptr<uint64_t>(ws, L.part[2]);
-    uint64_t* p3 = ws_ptr<uint64_t>(ws, L.part[3]);
-    u32x4* dense = ws_ptr<u32x4>(ws, L.dense);
+    uint64_t* hdr = ws_ptr<uint64_t>(ws, L.t.hdr);
+    uint64_t* part[4];
+    for (int p = 0; p < 4; ++p) part[p] = ws_ptr<uint64_t>(ws, L.t.part[p]);
+    u32x4* dense = ws_ptr<u32x4>(ws, L.t.dense);
     uint64_t* ping = ws_ptr<uint64_t>(ws, L.keys[0]);
     uint64_t* pong = ws_ptr<uint64_t>(ws, L.keys[1]);
     uint64_t* keys = ws_ptr<uint64_t>(ws, L.keys[2]);
@@ -607,11 +496,15 @@ int cfws_h2_streams_batch(const uint64_t* d_starts, const cfws_h2_frame_info_t* 
     RunRow* runs = ws_ptr<RunRow>(ws, L.runs);
     uint32_t* tile_passes = ws_ptr<uint32_t>(ws, L.tile_passes);
     uint32_t* dfirst = ws_ptr<uint32_t>(ws, L.dfirst);
-    const uint32_t nb = grid_for(n, kStGroup), rows = grid_for(n, kThreads);
+    // the block sums of StRecords are free again when StClosed needs a pair
+    const StRecords records = {d_info, n, {part[0]}, dense};
+    const StRuns group_runs = {dense, keys, hdr, dfirst, conns, {part[1], part[2]}, runs, run_of};
+    const StClosed closed = {dense, keys, runs, hdr, {part[0], part[3]}, d_msgs, d_stream_first, d_counts};
+    const uint32_t nb = grid_for(n, kTableGroup), rows = grid_for(n, kThreads);
     // the dense list's length is on the device: the grids cover n_frames rows
-    h2streams_count_kernel<<<nb, kThreads, 0, st>>>(d_info, n, p0);
-    scan_partials_kernel<<<1, kThreads, 0, st>>>(p0, nb, hdr + kHdrData);
-    h2streams_compact_kernel<<<nb, kThreads, 0, st>>>(d_info, n, p0, dense);
+    table_pass_kernel<kTableReduce><<<nb, kThreads, 0, st>>>(records);
+    scan_partials_kernel<<<1, kThreads, 0, st>>>(part[0], nb, hdr + kHdrData);
+    table_pass_kernel<kTableApply><<<nb, kThreads, 0, st>>>(records);
     h2streams_conn_rows_kernel<<<grid_for(conns + 1, kThreads), kThreads, 0, st>>>(dense, hdr, d_conn_first, conns, n,
                                                                                   dfirst);
     h2streams_sort_kernel<<<grid_for(n, kSortTile), kThreads, 0, st>>>(dense, hdr, dfirst, conns, ping, keys,
@@ -619,13 +512,12 @@ int cfws_h2_streams_batch(const uint64_t* d_starts, const cfws_h2_frame_info_t* 
     for (uint32_t p = 0; p < L.passes; ++p)
         h2streams_merge_kernel<<<rows, kThreads, 0, st>>>(hdr, dfirst, conns, tile_passes, p, (p & 1) ? pong : ping,
                                                           (p & 1) ? ping : pong, keys);
-    h2streams_starts_kernel<<<nb, kThreads, 0, st>>>(dense, keys, hdr, dfirst, conns, p1, p2);
-    scan_partials2_kernel<<<2, kThreads, 0, st>>>(p1, p2, nb, hdr + kHdrRuns, hdr + kHdrBytes);
-    h2streams_runs_kernel<<<nb, kThreads, 0, st>>>(dense, keys, hdr, dfirst, conns, p1, p2, runs, run_of);
-    h2streams_closed_kernel<<<nb, kThreads, 0, st>>>(dense, keys, runs, hdr, p0, p3);
-    scan_partials2_kernel<<<2, kThreads, 0, st>>>(p0, p3, nb, hdr + kHdrClosed, hdr + kHdrClosedFrames);
-    h2streams_records_kernel<<<nb, kThreads, 0, st>>>(dense, keys, runs, hdr, p0, p3, d_msgs, d_stream_first,
-                                                      d_counts);
+    table_pass_kernel<kTableReduce><<<nb, kThreads, 0, st>>>(group_runs);
+    scan_partials2_kernel<<<2, kThreads, 0, st>>>(part[1], part[2], nb, hdr + kHdrRuns, hdr + kHdrBytes);
+    table_pass_kernel<kTableApply><<<nb, kThreads, 0, st>>>(group_runs);
+    table_pass_kernel<kTableReduce><<<nb, kThreads, 0, st>>>(closed);
+    scan_partials2_kernel<<<2, kThreads, 0, st>>>(part[0], part[3], nb, hdr + kHdrClosed, hdr + kHdrClosedFrames);
+    table_pass_kernel<kTableApply><<<nb, kThreads, 0, st>>>(closed);
     h2streams_order_kernel<<<rows, kThreads, 0, st>>>(d_starts, dense, keys, runs, run_of, hdr, d_order,
                                                       d_order_frame);
     if (d_conn_first_msg)
