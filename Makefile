@@ -7,7 +7,7 @@
 HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_handshake cfws_ops cfws_h2index cfws_messages cfws_h2streams cfws_uniform
+DEVSRC   := cfws_device cfws_plan cfws_slots cfws_h2 cfws_split cfws_relay cfws_keys cfws_handshake cfws_ops cfws_h2index cfws_messages cfws_h2streams cfws_utf8 cfws_uniform
 HOSTSRC  := cfws_frame cfws_pipeline cfws_index cfws_graph
 HDR      := include/cfws.h include/cfws_co_ws_frame.h coldforce_amd/csrc/cfws_internal.h coldforce_amd/csrc/cfws_rules.h coldforce_amd/csrc/cfws_chunks.h coldforce_amd/csrc/cfws_keyrules.h coldforce_amd/csrc/cfws_keydev.h coldforce_amd/csrc/cfws_devpolicy.h
 LIB      := coldforce_amd/libcfws.so
@@ -79,6 +79,21 @@ build/messages_asan: tests/native/messages_asan.cpp coldforce_amd/csrc/cfws_inde
 	$(HIPCC) -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Icoldforce_amd/csrc -o $@ \
 	    tests/native/messages_asan.cpp coldforce_amd/csrc/cfws_index.cpp
+
+# the host UTF-8 check (cfws_utf8_check_messages, cfws_index.cpp alone) in a
+# stand-alone host program under AddressSanitizer + UBSan;
+# tests/test_utf8_host.py builds and runs it
+build/utf8_asan: tests/native/utf8_asan.cpp coldforce_amd/csrc/cfws_index.cpp $(HDR)
+	@mkdir -p build
+	$(HIPCC) -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Icoldforce_amd/csrc -o $@ \
+	    tests/native/utf8_asan.cpp coldforce_amd/csrc/cfws_index.cpp
+
+# tools/utf8_bench.py's host leg (threads of cfws_utf8_check_messages calls)
+build/libutf8hostwalk.so: tools/utf8_host_walk.cpp $(LIB) $(HDR)
+	@mkdir -p build
+	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -Iinclude -o $@ $< -Lcoldforce_amd -lcfws \
+	    -Wl,-rpath,'$$ORIGIN/../coldforce_amd' -lpthread
 
 # the host stream grouping (cfws_h2_streams_from_frames, cfws_index.cpp alone)
 # in a stand-alone host program under AddressSanitizer + UBSan;

@@ -73,6 +73,8 @@ BATCH_SYMBOLS = (
     "cfws_pipeline_h2_receive",
     "cfws_messages_from_frames", "cfws_messages_workspace_size", "cfws_messages_group_frames",
     "cfws_messages_batch",
+    "cfws_utf8_check_messages", "cfws_utf8_workspace_size", "cfws_utf8_piece_bytes", "cfws_utf8_wave_bytes",
+    "cfws_utf8_workgroup_bytes", "cfws_utf8_messages_batch",
     "cfws_h2_streams_from_frames", "cfws_h2_streams_workspace_size", "cfws_h2_streams_group_frames",
     "cfws_h2_streams_batch",
 )
@@ -201,6 +203,12 @@ def lib(path: str = LIB_PATH) -> C.CDLL:
         "cfws_messages_group_frames": ([], _sz),
         "cfws_messages_batch": ([_vp, _vp, _sz, _vp, _sz, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _sz, _vp],
                                 C.c_int),
+        "cfws_utf8_check_messages": ([_vp, _u64, _vp, _sz, _vp, _vp, _vp, _sz, _vp], _sz),
+        "cfws_utf8_workspace_size": ([_sz], _sz),
+        "cfws_utf8_piece_bytes": ([], _sz),
+        "cfws_utf8_wave_bytes": ([], _sz),
+        "cfws_utf8_workgroup_bytes": ([], _sz),
+        "cfws_utf8_messages_batch": ([_vp, _u64, _vp, _sz, _vp, _vp, _vp, _u64, _vp, _vp, _sz, _vp], C.c_int),
         "cfws_h2_streams_from_frames": ([_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp], _sz),
         "cfws_h2_streams_workspace_size": ([_sz, _sz], _sz),
         "cfws_h2_streams_group_frames": ([], _sz),
@@ -1159,6 +1167,74 @@ def messages_batch(desc_t, status_t=None, conn_first_t=None, msgs_t=None, contro
 
 def messages_from_device(t) -> np.ndarray:
     return t.cpu().numpy().reshape(-1).view(MESSAGE_DTYPE).copy()
+
+
+# ---- UTF-8 check of received text messages -------------------------------------
+UTF8_CHECKED, UTF8_VALID, UTF8_TRUNCATED, UTF8_INVALID, UTF8_BAD = 1, 2, 4, 8, 16
+UTF8_CARRY_TEXT = 0x80000000
+
+# cfws_utf8_result_t, 16 bytes.
+UTF8_RESULT_DTYPE = np.dtype([("prefix", "<u8"), ("carry", "<u4"), ("flags", "u1"), ("zero8", "u1"),
+                              ("zero16", "<u2")])
+assert UTF8_RESULT_DTYPE.itemsize == 16
+
+
+def utf8_check_messages(payload, msgs: np.ndarray, carry_in: np.ndarray | None = None,
+                        bad_capacity: int | None = None, payload_bytes: int | None = None):
+    """Host UTF-8 check (cfws_utf8_check_messages) of the text messages among
+    msgs (MESSAGE_DTYPE rows) over the payload arena (bytes or a uint8 array):
+    (result, bad, n_checked, n_bad). result: UTF8_RESULT_DTYPE rows; bad holds
+    min(n_bad, bad_capacity) indices (the capacity defaults to the message
+    count); the counts are unclamped."""
+    arena = np.frombuffer(payload, np.uint8) if isinstance(payload, (bytes, bytearray)) else payload
+    rows = np.ascontiguousarray(msgs, dtype=MESSAGE_DTYPE)
+    n = rows.size
+    cin = None if carry_in is None else np.ascontiguousarray(carry_in, dtype=np.uint32)
+    cap = n if bad_capacity is None else bad_capacity
+    result = np.zeros(max(n, 1), dtype=UTF8_RESULT_DTYPE)
+    bad = np.zeros(max(cap, 1), dtype=np.uint32)
+    counts = np.zeros(2, dtype=np.uint64)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    nb = lib().cfws_utf8_check_messages(ptr(arena), arena.size if payload_bytes is None else payload_bytes, ptr(rows),
+                                        n, ptr(cin), ptr(result), ptr(bad), cap, ptr(counts))
+    assert nb == int(counts[1])
+    return result[:n], bad[:min(nb, cap)], int(counts[0]), int(nb)
+
+
+def utf8_workspace(n_msgs: int, device="cuda"):
+    import torch
+    return torch.empty(lib().cfws_utf8_workspace_size(n_msgs), dtype=torch.uint8, device=device)
+
+
+def utf8_messages_batch(payload_t, payload_bytes: int, msgs_t, carry_in_t=None, result_t=None, bad_t=None,
+                        counts_t=None, ws_t=None, stream=None):
+    """UTF-8 check of the text messages among device-resident message rows
+    (cfws_utf8_messages_batch). payload_t: the receive's arena, readable to
+    round16(payload_bytes); msgs_t: (n, 32) uint8 rows (messages_batch's);
+    carry_in_t: int32 per message or None. Returns (result_t, bad_t, n_checked,
+    n_bad) -- the counts synchronise. result_t: (n, 16) uint8 rows
+    (utf8_results_from_device); bad_t: int32 message indices. result_t, bad_t
+    (n rows each), counts_t and the workspace are allocated when not given."""
+    import torch
+    n = msgs_t.shape[0]
+    dev = msgs_t.device
+    if result_t is None:
+        result_t = torch.empty((max(n, 1), 16), dtype=torch.uint8, device=dev)
+    if bad_t is None:
+        bad_t = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    if counts_t is None:
+        counts_t = torch.zeros(2, dtype=torch.int64, device=dev)
+    if ws_t is None:
+        ws_t = utf8_workspace(n, dev)
+    _check(lib().cfws_utf8_messages_batch(_p(payload_t), payload_bytes, _p(msgs_t), n, _p(carry_in_t), _p(result_t),
+                                          _p(bad_t), bad_t.numel(), _p(counts_t), _p(ws_t), ws_t.numel(),
+                                          _stream(stream)), "cfws_utf8_messages_batch")
+    checked, n_bad = counts_t.tolist()
+    return result_t, bad_t, int(checked), int(n_bad)
+
+
+def utf8_results_from_device(t) -> np.ndarray:
+    return t.cpu().numpy().reshape(-1).view(UTF8_RESULT_DTYPE).copy()
 
 
 # ---- handshake accept keys ---------------------------------------------------

@@ -11,7 +11,8 @@
 // Also the host form of the message and control tables of received frames
 // (cfws_messages_from_frames; device form: cfws_messages.hip), and of the
 // HTTP/2 stream grouping (cfws_h2_streams_from_frames; device form:
-// cfws_h2streams.hip).
+// cfws_h2streams.hip), and of the UTF-8 check of received text messages
+// (cfws_utf8_check_messages; device form: cfws_utf8.hip).
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -161,6 +162,51 @@ size_t cfws_messages_from_frames(const cfws_frame_desc_t* h_desc, const int32_t*
     }
     if (n_control) *n_control = nc;
     return m;
+}
+
+// The UTF-8 rule (cfws_rules.h) as a scalar walk: per checked message, the
+// carried bytes then its own, position by position with the functions the
+// kernel's lanes call (cfws_utf8.hip); runs of ASCII are stepped over eight
+// bytes at a time and a well-formed lead's continuation bytes with it.
+size_t cfws_utf8_check_messages(const void* h_payload, uint64_t payload_bytes, const cfws_message_t* h_msgs,
+                                size_t n_msgs, const uint32_t* h_carry_in, cfws_utf8_result_t* result,
+                                uint32_t* bad, size_t bad_capacity, uint64_t counts[2])
+{
+    const uint8_t* d = static_cast<const uint8_t*>(h_payload);
+    uint64_t checked = 0, n_bad = 0;
+    for (size_t m = 0; m < n_msgs; ++m) {
+        const cfws_message_t& msg = h_msgs[m];
+        const uint32_t cin = h_carry_in ? h_carry_in[m] : 0u;
+        result[m] = cfws_utf8_result_t{};
+        if (!utf8_selected(msg.opcode, msg.flags, msg.payload_off, msg.payload_size, payload_bytes, cin)) continue;
+        const uint32_t k = utf8_carried(msg.flags, cin);
+        const uint8_t* body = d + msg.payload_off;
+        const uint64_t n = k + msg.payload_size;
+        auto S = [&](uint64_t j) -> uint32_t { return j < k ? (cin >> (8u * j)) & 0xffu : body[j - k]; };
+        uint64_t i = 0;
+        uint32_t cls = kUtf8Fine;
+        while (i < n) {
+            if (i >= k) {
+                uint64_t w;
+                while (n - i >= 8 && (memcpy(&w, body + (i - k), 8), (w & 0x8080808080808080ull) == 0)) i += 8;
+                if (i == n) break;
+            }
+            const uint32_t b = S(i);
+            if (b < 0x80u) { ++i; continue; }
+            cls = utf8_at_by(S, n, i);
+            if (cls != kUtf8Fine) break;
+            i += 1 + (utf8_is_cont(b) ? 0u : utf8_lead_need(b));
+        }
+        const Utf8Row r = utf8_row(S, n, k, msg.flags, i, cls == kUtf8Truncated);
+        result[m] = cfws_utf8_result_t{r.prefix, r.carry, (uint8_t)r.flags, 0, 0};
+        ++checked;
+        if (r.flags & CFWS_UTF8_BAD) {
+            if (n_bad < bad_capacity) bad[n_bad] = (uint32_t)m;
+            ++n_bad;
+        }
+    }
+    if (counts) { counts[0] = checked; counts[1] = n_bad; }
+    return (size_t)n_bad;
 }
 
 // The stream rule (cfws_rules.h) as a sort and a walk: per connection the

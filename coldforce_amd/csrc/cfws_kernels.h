@@ -8,7 +8,7 @@
 // device indexing, copies, fills and the drop-in service; cfws_h2index.hip:
 // HTTP/2 device indexing; cfws_messages.hip: the message and control tables
 // of received frames; cfws_h2streams.hip: HTTP/2 DATA frames of many streams,
-// by message).
+// by message; cfws_utf8.hip: the UTF-8 check of received text messages).
 // Everything here is internal to each unit (anonymous namespace); what the
 // units share is defined once (namespace cfws_rt): the error state and the
 // pass timing in cfws_device.hip; the deserialize plan, the fused

@@ -236,4 +236,122 @@ __host__ __device__ __forceinline__ uint32_t h2_stream_msg_flags(bool closed, bo
            (padded ? CFWS_H2_STREAM_PADDED : 0u);
 }
 
+// The UTF-8 rule of cfws_utf8_check_messages / cfws_utf8_messages_batch
+// (include/cfws.h). THIS LIBRARY'S rule, not the reference's, which validates
+// no text; the standard defines it (Unicode Table 3-7, RFC 3629). It is
+// written position by position, so that a kernel lane decides every byte from
+// the 3 bytes before and the 3 after it and nothing scans over the bytes:
+//   * a byte outside 80..BF is a lead; utf8_lead_need: the continuation bytes
+//     it needs, kUtf8BadLead for C0, C1, F5..FF (and for "no byte");
+//   * utf8_lead_class: a lead is fine when its next `need` bytes exist and are
+//     80..BF, the second one narrowed by utf8_second_ok (no overlong forms,
+//     no surrogates, nothing above U+10FFFF); TRUNCATED when the bytes that
+//     exist pass but some are missing, else INVALID;
+//   * utf8_cont_owned: a continuation byte is fine when, walking back up to 3
+//     bytes, the first non-continuation byte is a lead that needs at least
+//     that many.
+// The longest well-formed prefix of a string ends at the smallest position
+// that is not fine, and the string is truncated iff that position is a
+// truncated lead. The host form walks with utf8_at_by; the device form
+// (cfws_utf8.hip) calls utf8_at on a lane's window of bytes; both make the
+// result row with utf8_selected, utf8_carried and utf8_row.
+constexpr uint32_t kUtf8Absent = 0x100u;        // no byte at this position
+constexpr uint32_t kUtf8BadLead = 4u;
+enum : uint32_t { kUtf8Fine = 0, kUtf8Invalid = 1, kUtf8Truncated = 2 };
+
+__host__ __device__ __forceinline__ bool utf8_is_cont(uint32_t b) { return (b & 0x1c0u) == 0x80u; }
+
+__host__ __device__ __forceinline__ uint32_t utf8_lead_need(uint32_t b)
+{
+    return b < 0x80u ? 0u : (b < 0xc2u ? kUtf8BadLead : (b < 0xe0u ? 1u : (b < 0xf0u ? 2u : (b < 0xf5u ? 3u : kUtf8BadLead))));
+}
+
+__host__ __device__ __forceinline__ bool utf8_second_ok(uint32_t lead, uint32_t b)
+{
+    const uint32_t lo = lead == 0xe0u ? 0xa0u : (lead == 0xf0u ? 0x90u : 0x80u);
+    const uint32_t hi = lead == 0xedu ? 0x9fu : (lead == 0xf4u ? 0x8fu : 0xbfu);
+    return b >= lo && b <= hi;
+}
+
+// The lead b with the bytes n1, n2, n3 after it (kUtf8Absent past the end).
+__host__ __device__ __forceinline__ uint32_t utf8_lead_class(uint32_t b, uint32_t n1, uint32_t n2, uint32_t n3)
+{
+    const uint32_t need = utf8_lead_need(b);
+    if (need == 0u) return kUtf8Fine;
+    if (need == kUtf8BadLead) return kUtf8Invalid;
+    if (n1 == kUtf8Absent) return kUtf8Truncated;
+    if (!utf8_second_ok(b, n1)) return kUtf8Invalid;
+    if (need == 1u) return kUtf8Fine;
+    if (n2 == kUtf8Absent) return kUtf8Truncated;
+    if (!utf8_is_cont(n2)) return kUtf8Invalid;
+    if (need == 2u) return kUtf8Fine;
+    if (n3 == kUtf8Absent) return kUtf8Truncated;
+    return utf8_is_cont(n3) ? kUtf8Fine : kUtf8Invalid;
+}
+
+// A continuation byte with the bytes p1, p2, p3 before it (p1 the nearest).
+__host__ __device__ __forceinline__ bool utf8_cont_owned(uint32_t p1, uint32_t p2, uint32_t p3)
+{
+    if (!utf8_is_cont(p1)) { const uint32_t n = utf8_lead_need(p1); return n != kUtf8BadLead && n >= 1u; }
+    if (!utf8_is_cont(p2)) { const uint32_t n = utf8_lead_need(p2); return n != kUtf8BadLead && n >= 2u; }
+    return !utf8_is_cont(p3) && utf8_lead_need(p3) == 3u;
+}
+
+__host__ __device__ __forceinline__ uint32_t utf8_at(uint32_t b, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t n1,
+                                                     uint32_t n2, uint32_t n3)
+{
+    if (utf8_is_cont(b)) return utf8_cont_owned(p1, p2, p3) ? kUtf8Fine : kUtf8Invalid;
+    return utf8_lead_class(b, n1, n2, n3);
+}
+
+// Position i < n of the string S(0 .. n - 1).
+template <typename At>
+__host__ __device__ __forceinline__ uint32_t utf8_at_by(At S, uint64_t n, uint64_t i)
+{
+    auto before = [&](uint64_t d) -> uint32_t { return i >= d ? S(i - d) : kUtf8Absent; };
+    auto after = [&](uint64_t d) -> uint32_t { return n - i > d ? S(i + d) : kUtf8Absent; };
+    return utf8_at(S(i), before(1), before(2), before(3), after(1), after(2), after(3));
+}
+
+// Is the message checked? carry: carry_in[m], 0 without carry_in.
+__host__ __device__ __forceinline__ bool utf8_selected(uint32_t opcode, uint32_t msg_flags, uint64_t off, uint64_t size,
+                                                       uint64_t payload_bytes, uint32_t carry)
+{
+    const bool text = opcode == 1u ||
+                      (opcode == 0u && (msg_flags & CFWS_MESSAGE_HEADLESS) && (carry & CFWS_UTF8_CARRY_TEXT));
+    return text && !(msg_flags & CFWS_MESSAGE_LOST_BYTES) && off + size >= off && off + size <= payload_bytes;
+}
+
+// The carried bytes in front of a checked message.
+__host__ __device__ __forceinline__ uint32_t utf8_carried(uint32_t msg_flags, uint32_t carry)
+{
+    return (msg_flags & CFWS_MESSAGE_HEADLESS) ? (carry >> 24) & 3u : 0u;
+}
+
+// A checked message's row: S is the k carried bytes then the message's, n
+// bytes in all; start == n when every position is fine, else the first one
+// that is not, a truncated lead or not.
+struct Utf8Row {
+    uint64_t prefix;
+    uint32_t carry, flags;
+};
+
+template <typename At>
+__host__ __device__ __forceinline__ Utf8Row utf8_row(At S, uint64_t n, uint32_t k, uint32_t msg_flags, uint64_t start,
+                                                     bool truncated)
+{
+    Utf8Row r = {(start > k ? start : k) - k, 0u, CFWS_UTF8_CHECKED};
+    if (start == n) {
+        r.flags |= CFWS_UTF8_VALID;
+    } else if (truncated) {
+        const uint32_t cnt = (uint32_t)(n - start);                  // 1..3
+        for (uint32_t j = 0; j < cnt; ++j) r.carry |= (S(start + j) & 0xffu) << (8u * j);
+        r.carry |= cnt << 24;
+        r.flags |= CFWS_UTF8_TRUNCATED | ((msg_flags & CFWS_MESSAGE_OPEN) ? 0u : CFWS_UTF8_BAD);
+    } else {
+        r.flags |= CFWS_UTF8_INVALID | CFWS_UTF8_BAD;
+    }
+    return r;
+}
+
 #endif

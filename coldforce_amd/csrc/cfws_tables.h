@@ -1,6 +1,6 @@
-// cfws_tables.h -- table passes: what cfws_messages.hip and cfws_h2streams.hip
-// are built from, written once. Only those two units
-// include it.
+// cfws_tables.h -- table passes: what cfws_messages.hip, cfws_h2streams.hip
+// and cfws_utf8.hip are built from, written
+// once. Only those three units include it.
 //
 // A table pass goes over the rows of a table, kTableItems consecutive rows per
 // thread. Each row is weighed into one or two 64-bit sums, and the sums are
